@@ -6,7 +6,7 @@ in HBM:  PartI descriptor on both fragments (2 x 5000 keypoints x 60 rotations x
 -> numpy-order invariant pooling -> mutual NN -> coarse rotation index -> PartII -> per-match
 hypotheses -> YOHO-O vote (<=1000 hypotheses).  Whole-job keypoints/s = 10000 * pairs / time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,10 @@ N > 1: one process per GPU; the checkpoint is broadcast once from rank 0 over RC
   --scaling weak (default): every rank runs its own pair per step (per-GPU work fixed);
   --scaling strong: a step is one sweep over a FIXED list of 64 pairs (8 synthetic scenes x 8 pairs) dealt to the ranks by
     yoho_amd.run_dataset.plan_shards (the dataset driver's plan); value = 64 * 10000 * steps / time.
-Besides the headline (descriptor + YOHO-O) the line carries
+A plain run sets up, runs W warm-up steps, times ONE region of exactly K steps and prints the headline (metric, value, unit,
+higher_is_better, dtype, ms_per_step = region time / K) with the per-rank times.  --dump-outputs DIR writes what the timed path
+returned for its last pair as DIR/<name>.npy (dump_outputs).  With --full (each leg can be switched off by its --no-* option) the
+headline is the median of --repeats (default 3) such regions with clock probes beside it, and the line also carries
   "sustained"  the same steps for >= 2 s behind >= 1 s of load, with the mean shader clock of probes spread over the region (the
                headline's 20 steps are a 0.1 s burst at boost clock);
   "yohoc"      the same step with the YOHO-C estimator (config 5: descriptor + 1000 RANSAC iterations, no PartII) in BOTH of its
@@ -52,6 +55,43 @@ BF16X3_EXEC_PER_ALG = 6.0 * 14.0 / 13.0   # bf16 MFMA flops issued per algorithm
 FOURIER_EXEC_PER_ALG = 244.0 / 780.0      # slab products per 8-channel chunk: sum_rho d^3 = 244 vs 60 x 13 = 780
 FP16_MFMA_PEAK = 2500.0         # TFLOP/s dense (v_mfma_f32_32x32x16_f16, same rate as bf16)
 NOMINAL_MHZ = 2400.0            # shader clock the peaks are quoted at (MI355X_MICROARCH.md)
+DUMP_EQV_ROWS = 512             # --dump-outputs: seeded sample of keypoint rows of each fragment's (K,32,60) descriptor
+
+
+def gconv_dtype(mode):
+    """the `dtype` of the line: the arithmetic of the PartI group conv"""
+    if mode == "bf16x3":
+        return "bf16x3 split (fp32-accurate, fp32 accumulate)"
+    if mode in ("fp16x2", "fgemm", "fgemm256", "fgemm128", "fgemm8"):
+        return "fp16x2 split (2^-22-accurate products, fp32 accumulate)"
+    return "f32"
+
+
+def dump_outputs(outdir, r):
+    """What the timed path returned for the last pair of its last step, as outdir/<name>.npy in float32 / float64: the registration
+    (transform; winner index, inlier count, match count), both fragments' invariant descriptors (inv_np), a fixed seeded sample of
+    DUMP_EQV_ROWS keypoint rows of each fragment's equivariant descriptor (the whole pair's are 77 MB) with the row indices, and - where
+    the path returns them (--staged, --in-flight 1) - match list, coarse rotation indices, quaternions and per-match transforms."""
+    os.makedirs(outdir, exist_ok=True)
+    host = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    arrays = {"trans": np.asarray(r.trans, dtype=np.float64),
+              "registration": np.array([r.best_h, r.best_count, r.matches], dtype=np.float64)}
+    for i, o in enumerate(r.eqv):
+        n = o["eqv"].shape[0]
+        rows = np.sort(np.random.RandomState(i).choice(n, min(DUMP_EQV_ROWS, n), replace=False))
+        arrays[f"eqv{i}_rows"] = rows.astype(np.float64)
+        arrays[f"eqv{i}_sample"] = host(o["eqv"][torch.from_numpy(rows).to(o["eqv"].device)])
+        if "inv_np" in o:
+            arrays[f"inv{i}"] = host(o["inv_np"])
+    for name in ("match", "dr_index", "quat", "trans_pre"):
+        v = getattr(r, name, None)
+        if v is not None:
+            arrays[name] = host(v)
+    arrays = {k: np.ascontiguousarray(a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs would write {total} bytes, more than 64 MB"
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def _issued_rows(d, cout, mode):
@@ -342,8 +382,13 @@ def main():
                          "or direct 2-way fp16 split MFMA")
     ap.add_argument("--partII", choices=["f32", "bf16x3", "fp16x2", "cgemm", "cgemm8"], default=os.environ.get("YOHO_PARTII", "fp16x2"),
                     help="arithmetic of the two PartII cone layers")
-    ap.add_argument("--repeats", type=int, default=3, help="the timed region (exactly --steps steps) is run this many times; ms_per_step / value are "
-                                                           "the median repeat, min / max are reported beside it")
+    ap.add_argument("--repeats", type=int, default=None, help="the timed region (exactly --steps steps) is run this many times; ms_per_step / value are "
+                                                              "the median repeat, min / max are reported beside it (default: 3 with --full, else 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: clock / power readings, the sustained, selected-hypotheses, fgemm8 and YOHO-C legs, per-kernel "
+                         "roofline with in-run traffic, the dataset and raw-cloud legs and the CPU baseline (each can be left out by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its last pair as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--partI-schedule", default=os.environ.get("YOHO_PARTI_CHUNK", DEFAULT_SCHEDULE),
                     help="PartI pass: '0' breadth-first, 'C' or 'CxS' depth-first over chunks of C keypoints on S (1 or 2) streams")
     ap.add_argument("--no-dataset", action="store_true", help="skip the dataset-scale leg (tools/bench_dataset.py: 60 fragments from disk, ~500 pairs)")
@@ -351,6 +396,7 @@ def main():
     ap.add_argument("--no-traffic", action="store_true", help="skip the in-run PMC measurement of roofline.traffic (two short rocprofv3 child processes)")
     ap.add_argument("--no-sustained", action="store_true", help="skip the sustained leg (>= 1 s of load, then >= 2 s of timed steps)")
     args = ap.parse_args()
+    repeats = args.repeats if args.repeats is not None else (3 if args.full else 1)
     sched = [int(v) for v in str(args.partI_schedule).lower().split("x")] + [1]
     sched_chunk, sched_streams = sched[0], sched[1]
 
@@ -420,10 +466,16 @@ def main():
                                   hypotheses=hypotheses)
         return r
 
-    mon = PowerMonitor(dev)
+    class _NoMonitor:
+        source = cap_w = None
+
+        def read_once(self):
+            return {"sclk_mhz": None, "power_w": None}
+    # a plain run reads neither the SMU nor the clock probes: nothing but the headline's steps
+    mon = PowerMonitor(dev) if args.full else _NoMonitor()
     if os.environ.get("YOHO_BENCH_SMU", "1") == "0":
         mon.source = None                                  # no SMU sampling thread (diagnostics)
-    PROBE_US = int(os.environ.get("YOHO_BENCH_PROBE_US", "20"))       # 0 switches the device-side clock probes off
+    PROBE_US = int(os.environ.get("YOHO_BENCH_PROBE_US", "20")) if args.full else 0       # 0 switches the device-side clock probes off
     PROBES_PER_STEP = float(os.environ.get("YOHO_BENCH_PROBES_PER_STEP", "4"))
 
     class _NoProbe:
@@ -472,8 +524,39 @@ def main():
         return int(ctx.range_fallbacks + (sum(c.range_fallbacks for c in streamer.desc + [streamer.est]) if streamer else 0))
 
     g0 = guard_total()
-    dt, dts, rank_dts, res_timed, power_steps = timed("yohoo", args.steps, max(args.warmup, 1), args.repeats)
+    dt, dts, rank_dts, res_timed, power_steps = timed("yohoo", args.steps, max(args.warmup, 1), repeats)
     headline_range_repeats = guard_total() - g0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res_timed)
+    head = {
+        "metric": "keypoints/sec (5000 kp x60 rot desc+YOHO-O)",
+        "value": round(pairs_per_step * 2 * KP * args.steps / dt, 1),
+        "unit": "keypoints/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "ms_per_step_repeats": {"n": len(dts), "min": round(min(dts) / args.steps * 1e3, 3), "median": round(dt / args.steps * 1e3, 3),
+                                "max": round(max(dts) / args.steps * 1e3, 3),
+                                "all_in_order": [round(v / args.steps * 1e3, 3) for v in dts],
+                                "note": "every repeat times exactly --steps steps between barriers; value / ms_per_step are the median repeat"},
+        "ranks": {"world_size_seen": world, "process_group": bool(ydist.active()),
+                  "backend": (torch.distributed.get_backend() if ydist.active() else None),
+                  "ms_per_step_per_rank": {"min": round(min(rank_dts) / args.steps * 1e3, 3), "mean": round(float(np.mean(rank_dts)) / args.steps * 1e3, 3),
+                                           "max": round(max(rank_dts) / args.steps * 1e3, 3), "all": [round(v / args.steps * 1e3, 3) for v in rank_dts]},
+                  # what every rank was given and how long its share took (one step = one sweep over its pairs); under --scaling strong the
+                  # shares come from run_dataset.plan_shards, whose predicted max / mean load is printed beside the measured one
+                  "pairs_per_rank": [sum(len(pos) for _, pos in part) for part in full_plan] if full_plan else [1] * world,
+                  "ms_per_rank": [round(v / args.steps * 1e3, 3) for v in rank_dts],
+                  "plan_predicted_imbalance": round(max(plan_cost) / (sum(plan_cost) / len(plan_cost)), 4) if plan_cost else 1.0,
+                  "measured_imbalance": round(max(rank_dts) / (sum(rank_dts) / len(rank_dts)), 4)},
+        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+        "dtype": gconv_dtype(args.gconv), "data": "synthetic",
+    }
+    if not args.full and not args.timed_only:
+        if rank == 0:
+            print(json.dumps(dict(head, gconv=args.gconv, partII=args.partII, pairs_in_flight=args.in_flight, headline_range_repeats=headline_range_repeats)),
+                  flush=True)
+        ydist.barrier()
+        return
     if args.timed_only:
         if rank == 0:
             print(json.dumps({"metric": "keypoints/sec (5000 kp x60 rot desc+YOHO-O)", "value": round(pairs_per_step * 2 * KP * args.steps / dt, 1),
@@ -485,7 +568,7 @@ def main():
     # the last timed pair once more through the staged entries (untimed) with the vote order of its seed: the stage outputs the legs
     # below need (match list, coarse rotations, descriptors), and the check that the one-call pair of the timed steps picked the same
     # winner and transform
-    last_seed = 1000 + 100000 * (max(1, args.repeats) - 1) + args.steps * len(mine) - 1
+    last_seed = 1000 + 100000 * (max(1, repeats) - 1) + args.steps * len(mine) - 1
     res = pipeline.run_pair(ctx, *mine[-1], inlier_dist=0.09, max_iter=1000, order_rng=np.random.RandomState(last_seed & 0xFFFFFFFF))
     one_call = {"estimator_side": "staged entries composed in Python (pipeline.run_pair)" if (args.staged or streamer is None) else
                                   "one library call per pair (yoho_register_pair)",
@@ -726,7 +809,6 @@ def main():
             roof = {"bound": "mfma", "achieved": round(achieved, 2), "peak": FP32_MFMA_PEAK, "unit": "TFLOP/s",
                     "frac": round(achieved / FP32_MFMA_PEAK, 4), "traffic": None, "traffic_replayed": pmc_traffic("f32")[0],
                     "kernel": "gconv_kernel<15,false> (4 launches = 4 PartI layers, 2.1725 algorithmic TFLOP per 5000 kp)"}
-            dtype = "f32"
         elif args.gconv == "bf16x3":
             roof = {"bound": "mfma", "achieved": round(achieved, 2), "peak": BF16_MFMA_PEAK, "unit": "TFLOP/s",
                     "frac": round(achieved / BF16_MFMA_PEAK, 4), "traffic": None, "traffic_replayed": pmc_traffic("bf16x3")[0],
@@ -735,7 +817,6 @@ def main():
                     "executed_frac": round(achieved * BF16X3_EXEC_PER_ALG / BF16_MFMA_PEAK, 4),
                     "note": "achieved = algorithmic fp32-equivalent FLOP/s; the fp32-accurate bf16 split issues 6.46 bf16 MFMA flops "
                             "per algorithmic flop, so frac <= 0.155 for this formulation"}
-            dtype = "bf16x3 split (fp32-accurate, fp32 accumulate)"
         elif args.gconv == "fp16x2":
             roof = {"bound": "mfma", "achieved": round(achieved, 2), "peak": BF16_MFMA_PEAK, "unit": "TFLOP/s",
                     "frac": round(achieved / BF16_MFMA_PEAK, 4), "traffic": None, "traffic_replayed": pmc_traffic("fp16x2")[0],
@@ -744,7 +825,6 @@ def main():
                     "executed_frac": round(achieved * BF16X3_EXEC_PER_ALG / 2 / BF16_MFMA_PEAK, 4),
                     "note": "achieved = algorithmic fp32-equivalent FLOP/s; the 2-way fp16 split (x = hi + lo, 3 products, error "
                             "<= 3*2^-22 per product) issues 3.23 fp16 MFMA flops per algorithmic flop, so frac <= 0.31"}
-            dtype = "fp16x2 split (2^-22-accurate products, fp32 accumulate)"
         elif args.gconv in ("fgemm", "fgemm256", "fgemm128", "fgemm8"):
             # ONE definition: the fp16 MFMA flops the formulation needs - the irrep GEMMs (244 / 780 of the direct
             # multiply-adds), every product as 3 fp16 MFMA products, NO padding rows or columns - over the dense fp16 peak
@@ -810,7 +890,6 @@ def main():
                                     "note": "the reference's direct 13-tap flop count (4.345 TFLOP per 10000 kp) over the same launches: what rounds 1-3 "
                                             "reported as `frac`; not a hardware utilisation (the kernel does 244/780 of those multiply-adds, as 3 products each)"},
                     "conv_total_ms": round(conv_total_ms, 3)}
-            dtype = "fp16x2 split (2^-22-accurate products, fp32 accumulate)"
         else:
             ex = achieved * FOURIER_EXEC_PER_ALG
             roof = {"bound": "mfma", "achieved": round(achieved, 2), "peak": FP32_MFMA_PEAK, "unit": "TFLOP/s",
@@ -822,29 +901,8 @@ def main():
                             "244/780 of those flops on v_mfma_f32_32x32x2_f32, so frac can exceed 1; executed_frac is the "
                             "fraction of the fp32-MFMA peak actually sustained. The transform kernels between the layers are "
                             "timed separately (roofline_extra.transform_ms)"}
-            dtype = "f32"
         out = {
-            "metric": "keypoints/sec (5000 kp x60 rot desc+YOHO-O)",
-            "value": round(pairs_per_step * 2 * KP * args.steps / dt, 1),
-            "unit": "keypoints/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "ms_per_step_repeats": {"n": len(dts), "min": round(min(dts) / args.steps * 1e3, 3), "median": round(dt / args.steps * 1e3, 3),
-                                    "max": round(max(dts) / args.steps * 1e3, 3),
-                                    "all_in_order": [round(v / args.steps * 1e3, 3) for v in dts],
-                                    "note": "every repeat times exactly --steps steps between barriers; value / ms_per_step are the median repeat"},
-            "ranks": {"world_size_seen": world, "process_group": bool(ydist.active()),
-                      "backend": (torch.distributed.get_backend() if ydist.active() else None),
-                      "ms_per_step_per_rank": {"min": round(min(rank_dts) / args.steps * 1e3, 3), "mean": round(float(np.mean(rank_dts)) / args.steps * 1e3, 3),
-                                               "max": round(max(rank_dts) / args.steps * 1e3, 3), "all": [round(v / args.steps * 1e3, 3) for v in rank_dts]},
-                      # what every rank was given and how long its share took (one step = one sweep over its pairs); under --scaling strong the
-                      # shares come from run_dataset.plan_shards, whose predicted max / mean load is printed beside the measured one
-                      "pairs_per_rank": [sum(len(pos) for _, pos in part) for part in full_plan] if full_plan else [1] * world,
-                      "ms_per_rank": [round(v / args.steps * 1e3, 3) for v in rank_dts],
-                      "plan_predicted_imbalance": round(max(plan_cost) / (sum(plan_cost) / len(plan_cost)), 4) if plan_cost else 1.0,
-                      "measured_imbalance": round(max(rank_dts) / (sum(rank_dts) / len(rank_dts)), 4)},
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": dtype, "data": "synthetic",
+            **head,
             "config": {"workload": "one synthetic scene pair per step per GPU: 2 fragments x 5000 keypoints x 60 rotations x 32-D "
                                    "-> PartI group conv + invariant pooling -> mutual NN -> Des2R -> PartII -> YOHO-O (<=1000 hypotheses); "
                                    "random-init weights (seeded), inputs resident in HBM",

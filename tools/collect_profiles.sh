@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${RND}p
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-LEGS="--no-cpu-baseline --no-dataset --no-fcgf --no-sustained --no-traffic"
+LEGS="--full --no-cpu-baseline --no-dataset --no-fcgf --no-sustained --no-traffic"
 # 1. kernel trace of the bench command (pairs strictly one after the other, so that per-kernel durations are not inflated by overlap)
 rocprofv3 --kernel-trace --stats -d $O/prof_bench_seq -- python $R/bench.py $LEGS --repeats 1 --steps 10 --in-flight 1 > $O/bench_seq.json 2> $O/bench_seq.err
 python $R/tools/rocpd_stats.py $O/prof_bench_seq > $O/kernel_trace_bench_seq.md 2>&1

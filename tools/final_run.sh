@@ -8,7 +8,7 @@ timeout 600 python tools/stress_determinism.py 40 > $O/stress.log 2>&1; echo "st
 ( time timeout 2400 python -m pytest tests -m gpu -q -s --durations=15 ) > $O/pytest_gpu_final.log 2>&1; echo "pytest rc=$?"; grep -a 'CENSUS-SUMMARY\|passed\|failed\|^real' $O/pytest_gpu_final.log | tail -6
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
 timeout 1500 bash tools/collect_profiles.sh $C $RND > $O/collect.log 2>&1; echo "collect rc=$?"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc=$?"
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_final.json 2> $O/bench_final.err; echo "bench rc=$?"
 python - <<PY
 import json
 d=json.loads(open("$O/bench_final.json").read().strip().splitlines()[-1])
