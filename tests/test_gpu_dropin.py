@@ -330,6 +330,8 @@ def test_fcgf_extractor_dropin_and_full_yoho_extractor(sd1, tables):
     # call with every pass on the caller's stream (another split of the sixty rotations into passes is NOT bit-identical: the kernel
     # variants of a pass follow its row count, NOTEBOOK 9.6 - 8e-7 here)
     assert ex.lanes == 2 and ex._side_stream is not None
+    lanes = ex.fcgf.lanes(ex.lanes)                         # the lanes the call ran on (kept for the caller's stream)
+    assert len({st.cuda_stream for _, st in lanes}) == 2 and lanes[0][0] is not lanes[1][0] and lanes[1][1] is ex._side_stream
     for lanes, rb in ((1, 15),):
         ex.lanes, ex.rot_batch = lanes, rb
         np.random.seed(7)
@@ -341,10 +343,14 @@ def test_fcgf_extractor_dropin_and_full_yoho_extractor(sd1, tables):
     # next one): the values run() returns, fragment by fragment, with the generator consumed in the same order
     pcs = [pc, synth.surface_cloud(1900, seed=4), pc[:2000]]
     np.random.seed(11)
-    one = [ex.run(p, voxel_size=0.025, nkpts=48) for p in pcs]
+    one, one_feats = [], []
+    for p in pcs:
+        one.append(ex.run(p, voxel_size=0.025, nkpts=48))
+        one_feats.append(ex._last_group_feats.clone())
     np.random.seed(11)
     many = list(ex.run_many(pcs, voxel_size=0.025, nkpts=48))
     assert len(many) == 3
+    assert torch.equal(ex._last_group_feats, one_feats[-1])     # the group features of the fragment yielded last
     for a, b in zip(one, many):
         assert np.array_equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
     assert list(ex.run_many([])) == []
@@ -352,6 +358,7 @@ def test_fcgf_extractor_dropin_and_full_yoho_extractor(sd1, tables):
     np.random.seed(11)
     g = ex.run_many(pcs, voxel_size=0.025, nkpts=48)
     first = next(g)
+    assert torch.equal(ex._last_group_feats, one_feats[0])
     g.close()
     assert np.array_equal(first[0], one[0][0]) and torch.equal(first[2], one[0][2])
     np.random.seed(11)
@@ -655,6 +662,53 @@ def test_testset_create_from_point_clouds(tmp_path, tables):
             sel, Fg = fo.extract_features(pcg, 0.025, fsd)
             ref = orc.group_gather_one(kps[pid], pcg[sel].astype(np.float32), Fg, tables.R64[g])[0]
             assert rel(got[:, :, g], ref) < 1e-4, (pid, g)
+
+
+def test_testset_create_threads_end_with_no_fragments_and_on_a_loader_error(tmp_path):
+    """testset_create.Feature_extracting returns when there are no fragments, and raises the loader's error without hanging when
+    get_pc raises partway through (no fragment after it is read); its loader and writer threads have ended either way"""
+    import threading
+    from yoho_amd.YOHO_testset import testset_create
+    fsd = W.synth_state_dict(W.FCGF_SPEC, 3)
+    ck = {"config": {"model": "ResUNetBN2C", "model_n_out": 32, "normalize_feature": True, "conv1_kernel_size": 7}, "state_dict": fsd}
+    clouds = [synth.surface_cloud(1500, seed=31 + i) for i in range(2)]
+    read = []
+
+    def get_pc(i):
+        read.append(i)
+        if i == "2":
+            raise OSError("fragment 2 is unreadable")
+        return clouds[int(i) % 2]
+
+    class DS:
+        pc_ids = []
+
+    ds = DS()
+    ds.get_pc, ds.get_kps = get_pc, lambda i: clouds[int(i) % 2][:30]
+    cfg = types.SimpleNamespace(model=ck, voxel_size=0.025, dataset="synth", output_dir=str(tmp_path), origin_dir=str(tmp_path),
+                                datasets={"wholesetname": "synth", "room": ds})
+    tc = testset_create(cfg)
+
+    def outcome():                                          # on a thread of its own: a hang fails the test instead of stalling the suite
+        box = []
+
+        def target():
+            try:
+                tc.batch_feature_extraction()
+                box.append(None)
+            except BaseException as e:
+                box.append(e)
+        th = threading.Thread(target=target, daemon=True)
+        th.start()
+        th.join(120)
+        assert not th.is_alive(), "Feature_extracting did not return"
+        assert not [t.name for t in threading.enumerate() if t.name in ("testset-loader", "testset-writer")]
+        return box[0]
+
+    assert outcome() is None and tc.stats["fragments"] == 0
+    ds.pc_ids = ["0", "1", "2", "3", "4"]
+    err = outcome()
+    assert isinstance(err, OSError) and read == ["0", "1", "2"], (err, read)
 
 
 def test_dataset_driver_from_point_clouds_equals_the_cache_route(tmp_path, sd1, tables):

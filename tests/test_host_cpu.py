@@ -63,6 +63,49 @@ def test_extractor_pass_sizes_cover_the_group_once():
         assert ex._pass_starts(60) == want, rb
 
 
+def test_concurrent_stream_hands_out_a_held_stream_once(monkeypatch):
+    """hip.concurrent_stream keeps a registry of the streams it handed out: torch's round-robin pool deals a stream out again after
+    a turn, but one still held is never returned twice; a candidate the overlap probe rejected is tried again before anything new is
+    drawn (not against a stream it already failed with); a stream is handed out again once its holder has let go of it (with all of
+    the pool held, one is shared)"""
+    import gc
+    from yoho_amd import hip
+
+    class FakeStream:
+        def __init__(self, h):
+            self.cuda_stream = h
+
+    draws, probes = [], []
+
+    def stream(device=None):                           # a pool of four, dealt round-robin as torch does
+        draws.append(1 + len(draws) % 4)
+        return FakeStream(draws[-1])
+
+    def overlap(ctx, a, b):                            # 2 shares a hardware queue with the caller's stream
+        probes.append(b.cuda_stream)
+        return not (b.cuda_stream == 2 and a.cuda_stream == 0)
+
+    monkeypatch.setattr(torch.cuda, "Stream", stream)
+    monkeypatch.setattr(hip, "streams_overlap", overlap)
+    monkeypatch.setattr(hip, "_POOL_STREAMS", 4)
+    monkeypatch.setattr(hip, "_lent", {})
+    monkeypatch.setattr(hip, "_spare", {})
+    ctx, caller, other = types.SimpleNamespace(device=0), FakeStream(0), FakeStream(9)
+    a = hip.concurrent_stream(ctx, [caller])
+    b = hip.concurrent_stream(ctx, [caller])           # 2 is rejected and kept as a spare
+    assert (a.cuda_stream, b.cuda_stream, draws, probes) == (1, 3, [1, 2, 3], [1, 2, 3])
+    c = hip.concurrent_stream(ctx, [caller])           # the spare is not probed against the caller's stream again
+    assert c.cuda_stream == 4 and draws == [1, 2, 3, 4] and probes == [1, 2, 3, 4]
+    d = hip.concurrent_stream(ctx, [other])            # against another stream it is tried first: nothing new drawn
+    assert d.cuda_stream == 2 and draws == [1, 2, 3, 4] and probes == [1, 2, 3, 4, 2]
+    shared = hip.concurrent_stream(ctx, [other])       # a full turn of the pool finds only held streams: one is shared, not registered
+    assert draws == [1, 2, 3, 4, 1, 2, 3, 4, 1] and shared.cuda_stream == 1
+    del shared, a
+    gc.collect()
+    e = hip.concurrent_stream(ctx, [caller])           # 1 was let go of
+    assert e.cuda_stream == 1 and sorted(s.cuda_stream for s in (b, c, d, e)) == [1, 2, 3, 4]
+
+
 def test_lane_context_loads_the_backbone_once_per_context(monkeypatch):
     """fcgf_extractor.lane_context(): the second lane's context is process-wide (hip.get_context(lane=1)) and gets this backbone's
     weights when another object's are resident; a pass on it leaves the first context's residency alone"""

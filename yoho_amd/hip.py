@@ -6,6 +6,8 @@ library cannot be loaded, importing a GPU op raises.
 """
 import ctypes as C
 import os
+import sys
+import threading
 import warnings
 import numpy as np
 import torch  # must be imported before the library so that both share one HIP runtime (libamdhip64.so.7)
@@ -820,15 +822,57 @@ def streams_overlap(ctx, s1, s2, microseconds=300):
     return best < 1.6e-6 * microseconds
 
 
+_POOL_STREAMS = 32           # torch deals its streams round-robin from a pool of this many per device and priority
+_lent = {}                   # device -> {cuda_stream handle: stream} concurrent_stream has handed out
+_spare = {}                  # device -> {handle: (stream, handles it did not overlap)} drawn and rejected by the overlap probe
+_streams_lock = threading.Lock()                   # (the ranks of a sharded run pick their streams from threads of their own)
+
+
+def _draw(device, taken):
+    """a stream of torch's pool whose handle is not in `taken`; None after a full turn of the pool"""
+    for _ in range(_POOL_STREAMS):
+        s = torch.cuda.Stream(device=device)
+        if s.cuda_stream not in taken:
+            return s
+    return None
+
+
 def concurrent_stream(ctx, others, tries=8):
-    """a new torch stream (normal priority) that demonstrably overlaps every stream of `others` (streams_overlap): the first candidate
-    that passes is kept.  Falls back to the last candidate - correct, merely serialised - when none does."""
-    cand = None
-    for _ in range(tries):
-        cand = torch.cuda.Stream(device=ctx.device)
-        if all(streams_overlap(ctx, o, cand) for o in others):
-            return cand
-    return cand
+    """a torch stream (normal priority) that demonstrably overlaps every stream of `others` (streams_overlap) and that no other
+    holder of a stream from this function has: a fresh draw from torch's pool can be a stream handed out before (the backbone lanes,
+    the run_many tail, the testset copy stream, the dataset runner's copy and worker streams), and two components would then
+    serialise on one stream unnoticed - the probe only knows `others`.  A stream stays registered while an object of it handed out
+    here is referenced outside the registry (torch's stream objects cannot be watched by weak references: their deallocation leaves
+    them dangling).  Candidates the probe rejected are kept and tried again - unless they failed against one of `others` - before
+    `tries` fresh ones are drawn; when none passes, the last one probed is returned, and when every stream of the pool is held, a
+    shared one - correct, merely serialised."""
+    dev = ctx.device
+    with _streams_lock:
+        lent, spare = _lent.setdefault(dev, {}), _spare.setdefault(dev, {})
+        for h in list(lent):
+            if sys.getrefcount(lent[h]) <= 2:      # the registry's reference and the call's: let go of by its holder
+                del lent[h]
+        cand = None
+        for h in list(spare) + [None] * tries:
+            if h is None:
+                s, bad = _draw(dev, lent.keys() | spare.keys()), set()
+                if s is None:                      # every stream of the pool is lent or spare
+                    break
+            else:
+                s, bad = spare[h]
+                if any(o.cuda_stream in bad for o in others):
+                    continue                       # measured before: it shares a hardware queue with one of `others`
+            cand = s
+            failed = next((o for o in others if not streams_overlap(ctx, o, s)), None)
+            if failed is None:
+                break
+            bad.add(failed.cuda_stream)
+            spare[s.cuda_stream] = (s, bad)
+        if cand is None:
+            return torch.cuda.Stream(device=dev)
+        spare.pop(cand.cuda_stream, None)
+        lent[cand.cuda_stream] = cand
+        return cand
 
 
 def get_context(device=None, so3_dir=None, lane=0):
