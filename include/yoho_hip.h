@@ -405,6 +405,13 @@ int yoho_phase_read(yoho_ctx* ctx, double* ms, double* flops, double* launches, 
  * it on a stream of its own beside the kernels under test. */
 int yoho_clock_probe(yoho_ctx* ctx, int microseconds, long long* out3, void* stream);
 
+/* test hook, no reference counterpart: fills the context's whole workspace and pair scratch with the 32-bit `pattern` on `stream`
+ * and keeps the pattern: from then on every (re)allocation of either is filled with it before first use (on the stream of the call
+ * that grows it, ahead of any work that call forks to another stream).  Lets a test prove that no kernel reads scratch bytes it did
+ * not write.  A context never given a pattern fills nothing.  The workspace of the matching, grid-NN, estimator, pair and backbone
+ * entries holds indices and counts: a test poisons only contexts that run the PartI / PartII passes. */
+int yoho_poison_scratch(yoho_ctx* ctx, unsigned pattern, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,7 @@ def test_every_entry_point_refuses_bad_arguments(env, hip):
         ("yoho_phase_read", (h, N, N, N, N), EINVAL, "yoho_phase_read"),
         ("yoho_clock_probe", (h, 0, p(i64(3)), N), EINVAL, "yoho_clock_probe"),
         ("yoho_clock_probe", (h, 20, N, N), EINVAL, "yoho_clock_probe"),
+        ("yoho_poison_scratch", (N, 0xFFFFFFFF, N), EINVAL, "yoho_poison_scratch"),
     ]
     seen = set()
     for name, args, code, text in cases:

@@ -464,6 +464,7 @@ def test_partII_ragged_match_counts(ctx, ctxh, sd2, tables, M):
     qo = orc.partII_forward(a, b, c_, d, dr, sd2, tables.N, tables.P)
     assert q.shape == (M, 4) and np.isfinite(q).all()
     assert rel(q, qo) < TOL and rel(q32, qo) < TOL, (rel(q, qo), rel(q32, qo))
+    assert ctxh.range_fallbacks == 0 and ctxh.range_repeats["partII"] == 0, ctxh.range_report()      # no pass repeated in bf16x3
 
 
 @pytest.mark.parametrize("mode,tol", [("cgemm", TOL), ("cgemm8", TOL)])
@@ -472,7 +473,8 @@ def test_partII_cone_gemm_modes(hip, ctx, ctxh, sd1, sd2, tables, mode, tol):
     cone elements the inverse transform leaves, fp16x2 products or fp16 main product + fp8 correction products) against the oracle, the
     fp32 kernels and the direct cone kernel of mode 2 - at match counts around every tile boundary of the new kernels (32-match transform
     tiles, 16-match cone1 tiles, 256-match column tiles: the last column tile of a pass is ragged and its unwritten columns must not
-    leak), through the plain and the row-indexed entry, and repeated (workspace reuse with stale column tiles from a larger pass)."""
+    leak: the scratch is poisoned with the largest finite fp16 before every ragged pass, and no pass may raise the range flag), through
+    the plain and the row-indexed entry, and repeated (workspace reuse with stale column tiles from a larger pass)."""
     c = hip.Context()
     c.load_partI(sd1)
     c.load_partII(sd2)
@@ -485,7 +487,10 @@ def test_partII_cone_gemm_modes(hip, ctx, ctxh, sd1, sd2, tables, mode, tol):
         a, b, c_, d = (np.ascontiguousarray(x[700 - M:]) for x in feats)
         dr = rs.randint(0, 60, size=M).astype(np.int64)
         args = [cu(x) for x in (a, b, c_, d)]
+        if M != 700:
+            c.poison_scratch(0x7BFF7BFF)                          # the largest finite fp16 in every unwritten byte, not valid stale data
         q = c.partII_forward(*args, cu(dr)).cpu().numpy()
+        assert c.range_fallbacks == 0 and c.range_repeats["partII"] == 0, (M, c.range_report())
         qd = ctxh.partII_forward(*args, cu(dr)).cpu().numpy()     # the direct cone kernel (pinned to the oracle by the tests above)
         assert q.shape == (M, 4) and np.isfinite(q).all()
         assert rel(q, qd) < tol, (M, rel(q, qd))
@@ -493,7 +498,10 @@ def test_partII_cone_gemm_modes(hip, ctx, ctxh, sd1, sd2, tables, mode, tol):
             qo = orc.partII_forward(a, b, c_, d, dr, sd2, tables.N, tables.P)
             worst = max(worst, rel(q, qo))
             assert rel(q, qo) < tol, (M, rel(q, qo))
+        if M != 700:
+            c.poison_scratch(0x7BFF7BFF)
         assert np.array_equal(q, c.partII_forward(*args, cu(dr)).cpu().numpy()), M          # same bits on a repeat
+        assert c.range_fallbacks == 0 and c.range_repeats["partII"] == 0, (M, c.range_report())
     print("partII %s: worst rel err vs oracle %.3g" % (mode, worst))
     # the row-indexed entry (what run_pair / yoho_register_pair use): rows addressed through a match list
     K = 300

@@ -211,6 +211,9 @@ int ensure_ws(yoho_ctx* ctx, size_t bytes, hipStream_t s) {
         return YOHO_ENOMEM;
     }
     ctx->ws.bytes = want;
+    // a poisoned context (yoho_poison_scratch) fills every new allocation before first use, on the caller's stream: work the pass
+    // forks to a second stream starts behind it
+    if (ctx->poison) HIPCHK(hipMemsetD32Async(ctx->ws.p, (int)ctx->poison_pattern, want / 4, s));
     return 0;
 }
 
@@ -538,6 +541,17 @@ int yoho_set_fcgf_sort(yoho_ctx* c, int parity_sort, int cell_sort) {
 int yoho_set_nn_grid(yoho_ctx* c, double cell) {
     if (!c || !(cell >= 0.0) || !std::isfinite(cell)) { set_error("yoho_set_nn_grid: cell must be a finite number >= 0 (0 = brute force)"); return YOHO_EINVAL; }
     c->nn_cell = cell;
+    return 0;
+}
+
+int yoho_poison_scratch(yoho_ctx* c, unsigned pattern, void* stream) {
+    if (!c) { set_error("yoho_poison_scratch: null ctx"); return YOHO_EINVAL; }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    c->poison = true;
+    c->poison_pattern = pattern;
+    if (c->ws.p) HIPCHK(hipMemsetD32Async(c->ws.p, (int)pattern, c->ws.bytes / 4, s));
+    if (c->pair_ws) HIPCHK(hipMemsetD32Async(c->pair_ws, (int)pattern, c->pair_ws_bytes / 4, s));
     return 0;
 }
 

@@ -304,6 +304,7 @@ struct yoho_ctx {
     // workspace (grown on demand)
     yoho::Workspace ws;
     void* pair_ws = nullptr; size_t pair_ws_bytes = 0;        // yoho_register_pair: device scratch that outlives the staged calls' use of ws
+    bool poison = false; unsigned poison_pattern = 0;          // yoho_poison_scratch (tests): ws / pair_ws are filled with the pattern when (re)allocated
     void* pair_host = nullptr; size_t pair_host_bytes = 0;    // ... and its page-locked host side (match count, vote order, result)
     // depth-first PartI schedule (default mode): the pass is cut into chunks of partI_chunk keypoints (a multiple of 256; 0 = one
     // breadth-first pass), each chunk running head -> 4 GEMMs + 3 transforms -> tail on its own slice of the workspace so that

@@ -888,7 +888,9 @@ __global__ __launch_bounds__(512, 2) void cgemm_kernel(CGemmArgs a) {
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi) {
         const int m = mt * 256 + nh * 128 + wn * 64 + bi * 32 + c32;     // match
-        const bool ok = (m >> 5) < a.nT32 && (m >> 4) < a.nTiles16;
+        // columns past the last 32-match tile were never written by the inverse transform (stale or foreign bytes): skipped before
+        // they reach the range word, as in fgemm3c
+        if ((m >> 5) >= a.nT32 || (m >> 4) >= a.nTiles16) continue;
 #pragma unroll
         for (int ai = 0; ai < 4; ++ai) {
 #pragma unroll
@@ -907,11 +909,9 @@ __global__ __launch_bounds__(512, 2) void cgemm_kernel(CGemmArgs a) {
                 unsigned h0, l0, h1, l1;
                 cg_split_pair(y[0], y[1], h0, l0);
                 cg_split_pair(y[2], y[3], h1, l1);
-                if (ok) {
-                    char* dst = a.out + (((size_t)(m >> 4) * a.c8out + (o >> 3)) * 2) * 15360 + g * 256 + (m & 15) * 16 + half * 8;
-                    *reinterpret_cast<uint2*>(dst) = uint2{h0, h1};
-                    *reinterpret_cast<uint2*>(dst + 15360) = uint2{l0, l1};
-                }
+                char* dst = a.out + (((size_t)(m >> 4) * a.c8out + (o >> 3)) * 2) * 15360 + g * 256 + (m & 15) * 16 + half * 8;
+                *reinterpret_cast<uint2*>(dst) = uint2{h0, h1};
+                *reinterpret_cast<uint2*>(dst + 15360) = uint2{l0, l1};
             }
         }
     }

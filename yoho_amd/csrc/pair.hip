@@ -182,6 +182,7 @@ static int pair_scratch(yoho_ctx* c, int n, PairScratch& p, hipStream_t s) {
         hipError_t e = hipMalloc(&c->pair_ws, off);
         if (e != hipSuccess) { set_error("pair scratch of %zu bytes: %s", off, hipGetErrorString(e)); return YOHO_ENOMEM; }
         c->pair_ws_bytes = off;
+        if (c->poison) HIPCHK(hipMemsetD32Async(c->pair_ws, (int)c->poison_pattern, off / 4, s));
     }
     const size_t host_need = 8 * N + 256;
     if (c->pair_host_bytes < host_need) {

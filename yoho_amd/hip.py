@@ -27,7 +27,7 @@ SYMBOLS = [
     "yoho_des2r", "yoho_des2r_indexed", "yoho_partII_forward", "yoho_partII_forward_indexed", "yoho_hyp_from_quat", "yoho_o_score", "yoho_c_ransac",
     "yoho_group_gather", "yoho_set_profiling", "yoho_get_kernel_ms", "yoho_set_gconv_mode", "yoho_set_partII_mode", "yoho_set_nn_grid",
     "yoho_range_status", "yoho_c_ransac_device", "yoho_group_scatter", "yoho_set_nn_prefilter", "yoho_set_fcgf_sort", "yoho_fcgf_voxelize_rotated_batch", "yoho_gconv_wgrad", "yoho_bn_stats", "yoho_bn_relu_apply", "yoho_bn_relu_backward", "yoho_set_partI_schedule", "yoho_clock_probe", "yoho_group_transfer_batch",
-    "yoho_register_pair", "yoho_vote_order", "yoho_c_draw_np", "yoho_phase_profile", "yoho_phase_read",
+    "yoho_register_pair", "yoho_vote_order", "yoho_c_draw_np", "yoho_phase_profile", "yoho_phase_read", "yoho_poison_scratch",
 ]
 
 
@@ -127,6 +127,7 @@ def load_library():
     lib.yoho_c_draw_np.argtypes = [vp, C.POINTER(ci), vp, vp, vp, ci, vp, C.POINTER(ci), C.POINTER(ci)]
     lib.yoho_phase_profile.argtypes = [vp, ci]
     lib.yoho_phase_read.argtypes = [vp, vp, vp, vp, vp]
+    lib.yoho_poison_scratch.argtypes = [vp, C.c_uint32, vp]
     for s in SYMBOLS[2:]:
         getattr(lib, s).restype = ci
     _lib = lib
@@ -437,6 +438,11 @@ class Context:
             if consume[i]:
                 self._range_pending[i] = False
         return out
+
+    def poison_scratch(self, pattern):
+        """test hook (yoho_poison_scratch): fill the workspace and the pair scratch with the 32-bit `pattern` on the current stream, now and
+        at every later (re)allocation.  Only for contexts that run nothing but PartI / PartII passes: the other entries keep indices there."""
+        _check(self._lib.yoho_poison_scratch(self._h, int(pattern) & 0xFFFFFFFF, _stream()))
 
     def partI_overflow(self):
         return self.range_status(consume=(True, False))[0]
