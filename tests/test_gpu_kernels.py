@@ -628,6 +628,9 @@ def test_kabsch_and_yohoc(ctx, gold):
     tri = orc.yohoc_draw_triples(dr, 200, np.random)
     it, cnt, Tc, dets = orc.yohoc_select(kk0, kk1, tri, 0.07)
     best_T, res, T_all, counts = ctx.c_ransac(cu(kk0), cu(kk1), cu(tri), cu((dets < 0).astype(np.uint8)), 0.07, want_all=True)
+    # a triple that repeats a match has a rank-1 / rank-0 covariance: the oracle's LAPACK answer for it is not the build's (the roll
+    # about the line is arbitrary), so those rows stay masked here; tests/test_gpu_estimators.py checks them against the exact
+    # reference (repeat2 / repeat3 / collinear families: frame, translation, objective and the count of the row's own transform)
     nodup = np.array([len(set(t)) == 3 for t in tri])
     ref_counts = np.array([orc.inlier_count(kk0, kk1, orc.threepps2tran(kk0[t], kk1[t])[0], 0.07) for t in tri])
     assert np.array_equal(counts.cpu().numpy()[nodup], ref_counts[nodup])

@@ -54,7 +54,10 @@ __global__ __launch_bounds__(256) void hyp_kernel(const float* __restrict__ quat
     double* o = T + (size_t)m * 12;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const double d = fma(p1[2], R[i * 3 + 2], fma(p1[1], R[i * 3 + 1], p1[0] * R[i * 3]));
+        // k1 @ R.T as the reference's numpy evaluates it (OpenBLAS dgemv on AVX2 / AVX-512 hosts): the product of index 1
+        // rounded, then indices 0 and 2 fused onto it.  Any order is within an ulp of the exact value; this one carries the
+        // reference's bits, which matters for keypoints far from the origin, where an ulp of t is large.
+        const double d = fma(p1[2], R[i * 3 + 2], fma(p1[0], R[i * 3], p1[1] * R[i * 3 + 1]));
         o[i * 4 + 0] = R[i * 3 + 0]; o[i * 4 + 1] = R[i * 3 + 1]; o[i * 4 + 2] = R[i * 3 + 2];
         o[i * 4 + 3] = __dsub_rn(p0[i], d);
     }
@@ -174,9 +177,11 @@ __device__ void kabsch3(const double* a0, const double* a1, bool reflect, double
             const double al = A[p] * A[p] + A[3 + p] * A[3 + p] + A[6 + p] * A[6 + p];
             const double be = A[q] * A[q] + A[3 + q] * A[3 + q] + A[6 + q] * A[6 + q];
             const double ga = A[p] * A[q] + A[3 + p] * A[3 + q] + A[6 + p] * A[6 + q];
-            const double lim = 1e-30 + 1e-16 * sqrt(al * be);
-            if (fabs(ga) > lim) {
-                offmax = fmax(offmax, fabs(ga) / (sqrt(al * be) + 1e-300));
+            // relative test only: an absolute floor would stop the rotations early for small triangles (the answer does
+            // not depend on the unit of length).  A column that is exactly 0 gives ga = 0 and is left alone.
+            const double nab = sqrt(al * be);
+            if (fabs(ga) > 1e-16 * nab) {
+                offmax = fmax(offmax, fabs(ga) / nab);
                 const double zeta = (be - al) / (2.0 * ga);
                 const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
                 const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
@@ -204,18 +209,24 @@ __device__ void kabsch3(const double* a0, const double* a1, bool reflect, double
     if (sg[i3] > sg[i2]) { const int t = i2; i2 = i3; i3 = t; }
     double u1[3], u2[3], u3[3], v1[3], v2[3], v3[3];
     double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    if (sg[i1] > 1e-300) {
+    if (sg[i1] > 1e-300) {      // rank 0 (one match three times, exactly): identity.  Only an underflow guard: sums of squares of
+                                // products of centred coordinates underflow long before (coordinates below ~1e-77)
 #pragma unroll
         for (int r = 0; r < 3; ++r) { u1[r] = A[r * 3 + i1] / sg[i1]; v1[r] = V[r * 3 + i1]; }
-        if (sg[i2] > 1e-13 * sg[i1]) {
+        bool rank2 = sg[i2] > 1e-13 * sg[i1];
+        if (rank2) {
 #pragma unroll
             for (int r = 0; r < 3; ++r) { u2[r] = A[r * 3 + i2] / sg[i2]; v2[r] = V[r * 3 + i2]; }
             // re-orthogonalise u2 against u1 (cheap insurance for nearly collinear triangles)
             const double d = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
             u2[0] -= d * u1[0]; u2[1] -= d * u1[1]; u2[2] -= d * u1[2];
             const double n = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
-            u2[0] /= n; u2[1] /= n; u2[2] /= n;
-        } else {            // rank 1 (two sampled matches coincide): roll about u1/v1 is arbitrary
+            // converged columns are orthogonal and n = 1 to rounding; a second column that was parallel to the first
+            // (rounding noise of a triple that is one point) leaves nothing to normalise: that is rank 1 (NaN fails the test too)
+            rank2 = n > 0.5;
+            if (rank2) { u2[0] /= n; u2[1] /= n; u2[2] /= n; }
+        }
+        if (!rank2) {       // rank 1 (two sampled matches coincide, or three collinear ones): roll about u1/v1 is arbitrary
             any_orthogonal(u1, u2);
             any_orthogonal(v1, v2);
         }
