@@ -1,4 +1,4 @@
-"""ctypes binding of libyoho_hip.so (include/yoho_hip.h) + a thin tensor-level wrapper.
+"""ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h) + a thin tensor-level wrapper.
 
 PyTorch-ROCm tensors are the device-memory container only: every method passes
 ``tensor.data_ptr()`` and the current HIP stream to the C ABI.  There is NO CPU fallback: if the
@@ -29,6 +29,9 @@ SYMBOLS = [
     "yoho_range_status", "yoho_c_ransac_device", "yoho_group_scatter", "yoho_set_nn_prefilter", "yoho_set_fcgf_sort", "yoho_fcgf_voxelize_rotated_batch", "yoho_gconv_wgrad", "yoho_bn_stats", "yoho_bn_relu_apply", "yoho_bn_relu_backward", "yoho_set_partI_schedule", "yoho_clock_probe", "yoho_group_transfer_batch",
     "yoho_register_pair", "yoho_vote_order", "yoho_c_draw_np", "yoho_phase_profile", "yoho_phase_read", "yoho_poison_scratch",
 ]
+# the entries of include/yoho_knn.h: a header and a list of their own, because the two ABI tests pin SYMBOLS to include/yoho_hip.h
+KNN_SYMBOLS = ["yoho_knn_search"]
+KNN_MAX = 16                                # YOHO_KNN_MAX
 
 
 class ConvW(C.Structure):
@@ -74,7 +77,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -128,7 +131,8 @@ def load_library():
     lib.yoho_phase_profile.argtypes = [vp, ci]
     lib.yoho_phase_read.argtypes = [vp, vp, vp, vp, vp]
     lib.yoho_poison_scratch.argtypes = [vp, C.c_uint32, vp]
-    for s in SYMBOLS[2:]:
+    lib.yoho_knn_search.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -563,6 +567,18 @@ class Context:
         dist = torch.empty((Ns,), dtype=torch.float32, device=src.device) if want_dist else None
         _check(self._lib.yoho_nn_search(self._h, _dev(src, torch.float32, "src"), Ns, _dev(tgt, torch.float32, "tgt"), Nt, D, 1 if squared else 0,
                                         C.c_void_p(idx.data_ptr()), C.c_void_p(dist.data_ptr()) if want_dist else None, _stream()))
+        return dist, idx
+
+    def knn_search(self, src, tgt, k, want_dist=True, squared=False):
+        """src (Ns,D), tgt (Nt,D) f32, D in {32,3}, 1 <= k <= min(KNN_MAX, Nt) -> (dist (Ns,k) f32 or None, idx (Ns,k) int64): the k
+        nearest rows of tgt, ascending by (distance as returned, index); column 0 is nn_search's answer (yoho_knn_search)."""
+        Ns, D = src.shape
+        Nt = tgt.shape[0]
+        k = int(k)
+        idx = torch.empty((Ns, k), dtype=torch.int64, device=src.device)
+        dist = torch.empty((Ns, k), dtype=torch.float32, device=src.device) if want_dist else None
+        _check(self._lib.yoho_knn_search(self._h, _dev(src, torch.float32, "src"), Ns, _dev(tgt, torch.float32, "tgt"), Nt, D, 1 if squared else 0, k,
+                                         C.c_void_p(idx.data_ptr()), C.c_void_p(dist.data_ptr()) if want_dist else None, _stream()))
         return dist, idx
 
     def mutual_nn(self, a, b):
