@@ -28,6 +28,34 @@ from .fcgf_feat import fcgf_extractor
 from .utils import make_non_exists_dir
 
 
+def group_features(fcgf, Rgroup, lanes, voxel_size, pc, keys, join=True):
+    """pc (N,3), keys (K,3) f64 -> (K,32,60) f32 cuda tensor (one fragment, all 60 group elements) on the backbone `fcgf` (an fcgf_extractor) with
+    the group `Rgroup` (60,3,3) over `lanes` backbone lanes; shared by testset_create and YOHO_Trainset.trainset_create.  Complete on the stream `join`:
+    True (the default) - the caller's current stream; a torch stream (Feature_extracting: its copy stream) - that stream, with
+    the caller's stream NOT made to wait for the lanes, so that the next fragment's first pass can be queued under this
+    fragment's last one."""
+    def prepare(pc_d):                                           # on lane 0's stream, before the first pass
+        k_d = torch.from_numpy(np.ascontiguousarray(np.asarray(keys, dtype=np.float64))).cuda()
+        out = torch.empty((k_d.shape[0], 32, 60), dtype=torch.float32, device="cuda")
+
+        def transfer(ctx, res, g0, Rs):
+            # rotated copies (pc @ R_g^T, :143) are never materialised: rotation, voxelisation and 'dspcd0' (the down-sampled
+            # points, .float(), :92) come out of one pass over the cloud (fcgf_extractor.extract_rotated_batch)
+            for j, (sel, feat, pts) in enumerate(res):
+                ctx.group_gather(k_d, pts, feat, g0 + j, out)    # keys @ R_g^T, f64 NN, feature row -> out[:, :, g]
+        return transfer, (pc_d, k_d, out)
+
+    nb = 15                                                      # rotated copies per backbone pass (split further by voxel count)
+    passes = [(g0, [Rgroup[g] for g in range(g0, g0 + nb)]) for g0 in range(0, 60, nb)]
+    done, (pc_d, k_d, out) = fcgf.rotated_passes(pc, passes, voxel_size, fcgf.lanes(lanes), prepare, draw_ahead=False)
+    st = torch.cuda.current_stream() if join is True else join
+    for e in done:
+        st.wait_event(e)
+    for x in (pc_d, k_d, out):                                   # released once `st` has run past the lanes' last use
+        x.record_stream(st)
+    return out
+
+
 class testset_create():
     def __init__(self, config, ctx=None):
         self.config = config
@@ -49,31 +77,9 @@ class testset_create():
             self.fcgf.lane_context()                                 # the second lane's weights are resident from here on, like the first one's
 
     def fragment_group_features(self, pc, keys, join=True):
-        """pc (N,3), keys (K,3) f64 -> (K,32,60) f32 cuda tensor (one fragment, all 60 group elements), complete on the stream `join`:
-        True (the default) - the caller's current stream; a torch stream (Feature_extracting: its copy stream) - that stream, with
-        the caller's stream NOT made to wait for the lanes, so that the next fragment's first pass can be queued under this
-        fragment's last one."""
-        def prepare(pc_d):                                           # on lane 0's stream, before the first pass
-            k_d = torch.from_numpy(np.ascontiguousarray(np.asarray(keys, dtype=np.float64))).cuda()
-            out = torch.empty((k_d.shape[0], 32, 60), dtype=torch.float32, device="cuda")
-
-            def transfer(ctx, res, g0, Rs):
-                # rotated copies (pc @ R_g^T, :143) are never materialised: rotation, voxelisation and 'dspcd0' (the down-sampled
-                # points, .float(), :92) come out of one pass over the cloud (fcgf_extractor.extract_rotated_batch)
-                for j, (sel, feat, pts) in enumerate(res):
-                    ctx.group_gather(k_d, pts, feat, g0 + j, out)    # keys @ R_g^T, f64 NN, feature row -> out[:, :, g]
-            return transfer, (pc_d, k_d, out)
-
-        nb = 15                                                      # rotated copies per backbone pass (split further by voxel count)
-        passes = [(g0, [self.Rgroup[g] for g in range(g0, g0 + nb)]) for g0 in range(0, 60, nb)]
-        done, (pc_d, k_d, out) = self.fcgf.rotated_passes(pc, passes, self.config.voxel_size, self.fcgf.lanes(self.lanes), prepare,
-                                                          draw_ahead=False)
-        st = torch.cuda.current_stream() if join is True else join
-        for e in done:
-            st.wait_event(e)
-        for x in (pc_d, k_d, out):                                   # released once `st` has run past the lanes' last use
-            x.record_stream(st)
-        return out
+        """pc (N,3), keys (K,3) f64 -> (K,32,60) f32 cuda tensor (one fragment, all 60 group elements): group_features on this object's
+        backbone, tables, lanes and voxel size"""
+        return group_features(self.fcgf, self.Rgroup, self.lanes, self.config.voxel_size, pc, keys, join)
 
     def Feature_extracting(self):
         import time

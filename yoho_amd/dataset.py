@@ -1,5 +1,6 @@
-"""Evaluation dataset description - drop-in for the test-time half of the reference's utils/dataset.py
-(EvalDataset / ThrDMatchPartDataset :21-143, get_dataset_name :146-229, get_dataset :232-238).
+"""Dataset description - drop-in for the fragment half of the reference's utils/dataset.py
+(EvalDataset / ThrDMatchPartDataset :21-143, get_dataset_name :146-229 - the test sets and the training set '3dmatch_train' that
+yoho_amd.YOHO_Trainset reads, get_dataset :232-238).
 
 The training Dataset classes (:242-323) are in yoho_amd.train.trainer.  open3d is not required: keypoints come from
 `Keypoints_PC/cloud_bin_{k}Keypoints.npy` when present (what the hot path reads), otherwise from the point
@@ -144,12 +145,38 @@ _SCENES = {    # utils/dataset.py:149-208 (scene list, fragments per scene)
 }
 
 
+# '3dmatch_train' (utils/dataset.py:216-221): 54 scenes, fragments per scene; six of them are held out for validation
+_TRAIN_SCENES = {
+    'bundlefusion-apt0': 85, 'rgbd-scenes-v2-scene_02': 8, 'bundlefusion-office1': 57, 'sun3d-brown_cogsci_1-brown_cogsci_1': 28,
+    'rgbd-scenes-v2-scene_06': 10, 'analysis-by-synthesis-apt2-kitchen': 9, 'rgbd-scenes-v2-scene_03': 8, 'bundlefusion-apt1': 84,
+    'sun3d-harvard_c8-hv_c8_3': 10, 'bundlefusion-copyroom': 44, 'sun3d-home_bksh-home_bksh_oct_30_2012_scan2_erika': 96,
+    'rgbd-scenes-v2-scene_04': 8, '7-scenes-pumpkin': 54, 'rgbd-scenes-v2-scene_01': 8, 'analysis-by-synthesis-office2-5a': 14,
+    'sun3d-brown_bm_1-brown_bm_1': 65, 'bundlefusion-apt2': 38, 'sun3d-brown_cs_2-brown_cs2': 52, 'bundlefusion-office2': 34,
+    'sun3d-hotel_sf-scan1': 92, 'sun3d-hotel_nips2012-nips_4': 62, 'bundlefusion-office3': 37, 'rgbd-scenes-v2-scene_09': 7,
+    'rgbd-scenes-v2-scene_05': 11, 'rgbd-scenes-v2-scene_07': 9, '7-scenes-heads': 18, 'sun3d-harvard_c3-hv_c3_1': 19,
+    'rgbd-scenes-v2-scene_08': 9, 'sun3d-mit_76_417-76-417b': 77, 'sun3d-mit_32_d507-d507_2': 54, 'sun3d-mit_46_ted_lab1-ted_lab_2': 75,
+    '7-scenes-chess': 54, 'rgbd-scenes-v2-scene_10': 7, 'sun3d-harvard_c11-hv_c11_2': 8, 'analysis-by-synthesis-apt2-living': 10,
+    'sun3d-mit_w20_athena-sc_athena_oct_29_2012_scan1_erika': 70, 'analysis-by-synthesis-apt1-living': 15,
+    'analysis-by-synthesis-apt1-kitchen': 11, 'sun3d-mit_dorm_next_sj-dorm_next_sj_oct_30_2012_scan1_erika': 26, '7-scenes-stairs': 24,
+    'sun3d-brown_bm_4-brown_bm_4': 32, 'bundlefusion-office0': 60, 'sun3d-harvard_c6-hv_c6_1': 15, 'rgbd-scenes-v2-scene_14': 6,
+    'rgbd-scenes-v2-scene_12': 7, 'analysis-by-synthesis-office2-5b': 17, 'analysis-by-synthesis-apt2-luke': 19, '7-scenes-office': 90,
+    'sun3d-harvard_c5-hv_c5_1': 20, 'sun3d-brown_cs_3-brown_cs3': 34, '7-scenes-fire': 36, 'rgbd-scenes-v2-scene_11': 6,
+    'analysis-by-synthesis-apt2-bed': 10, 'rgbd-scenes-v2-scene_13': 4,
+}
+_TRAIN_VALSCENES = ['sun3d-brown_bm_4-brown_bm_4', 'sun3d-harvard_c11-hv_c11_2', '7-scenes-heads', 'rgbd-scenes-v2-scene_10', 'bundlefusion-office0',
+                    'analysis-by-synthesis-apt2-kitchen']
+_SCENES['3dmatch_train'] = (list(_TRAIN_SCENES), list(_TRAIN_SCENES.values()))
+
+
 def get_dataset_name(dataset_name, origin_data_dir):
-    """utils/dataset.py:146-229 (test sets; '3dmatch_train' is a training set and out of scope)."""
+    """utils/dataset.py:146-229: {'wholesetname': name, scene: ThrDMatchPartDataset ...}; the training set '3dmatch_train' also carries
+    'valscenes', the scenes yoho_amd.YOHO_Trainset holds out for validation."""
     if dataset_name not in _SCENES:
         raise NotImplementedError
     scenes, stationnums = _SCENES[dataset_name]
     datasets = {'wholesetname': f'{dataset_name}'}
+    if dataset_name == '3dmatch_train':
+        datasets['valscenes'] = list(_TRAIN_VALSCENES)
     for scene, n in zip(scenes, stationnums):
         if dataset_name == '3dLomatch':        # shares 3dmatch's data, own ground truth (:179-182)
             root_dir = f'{origin_data_dir}/3dmatch/' + scene

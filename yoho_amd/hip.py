@@ -1,4 +1,4 @@
-"""ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h) + a thin tensor-level wrapper.
+"""ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h) + a thin tensor-level wrapper.
 
 PyTorch-ROCm tensors are the device-memory container only: every method passes
 ``tensor.data_ptr()`` and the current HIP stream to the C ABI.  There is NO CPU fallback: if the
@@ -32,6 +32,9 @@ SYMBOLS = [
 # the entries of include/yoho_knn.h: a header and a list of their own, because the two ABI tests pin SYMBOLS to include/yoho_hip.h
 KNN_SYMBOLS = ["yoho_knn_search"]
 KNN_MAX = 16                                # YOHO_KNN_MAX
+# the entries of include/yoho_trainset.h (training-set generation), kept apart for the same reason
+TRAINSET_SYMBOLS = ["yoho_radius_pairs", "yoho_trainset_gather"]
+RADIUS_MAX_POINTS = 1 << 20                 # YOHO_RADIUS_MAX_POINTS
 
 
 class ConvW(C.Structure):
@@ -77,7 +80,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -132,7 +135,9 @@ def load_library():
     lib.yoho_phase_read.argtypes = [vp, vp, vp, vp, vp]
     lib.yoho_poison_scratch.argtypes = [vp, C.c_uint32, vp]
     lib.yoho_knn_search.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS:
+    lib.yoho_radius_pairs.argtypes = [vp, vp, ci, vp, ci, C.c_float, vp, C.c_int64, vp, vp]
+    lib.yoho_trainset_gather.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -580,6 +585,40 @@ class Context:
         _check(self._lib.yoho_knn_search(self._h, _dev(src, torch.float32, "src"), Ns, _dev(tgt, torch.float32, "tgt"), Nt, D, 1 if squared else 0, k,
                                          C.c_void_p(idx.data_ptr()), C.c_void_p(dist.data_ptr()) if want_dist else None, _stream()))
         return dist, idx
+
+    def radius_pairs(self, a, b, radius):
+        """a (Na,3), b (Nb,3) f32 -> (M,2) int64: every (i, j) with |a_i - b_j| < radius in np.where's order (ascending i, then j), the
+        distance in f32 as include/yoho_trainset.h fixes it (yoho_radius_pairs).  One call with room for a few pairs per point and
+        one read of the count; a second call with the exact capacity only when that was short."""
+        Na, Nb = a.shape[0], b.shape[0]
+        pa, pb = _dev(a, torch.float32, "a"), _dev(b, torch.float32, "b")
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != 3 or b.shape[1] != 3:
+            raise ValueError("radius_pairs: a (Na,3), b (Nb,3)")
+        count = torch.empty((1,), dtype=torch.int64, device=a.device)
+        cap = 4 * max(Na, Nb)
+        while True:
+            pairs = torch.empty((cap, 2), dtype=torch.int64, device=a.device)
+            _check(self._lib.yoho_radius_pairs(self._h, pa, Na, pb, Nb, float(radius), C.c_void_p(pairs.data_ptr()) if cap else None, cap,
+                                               C.c_void_p(count.data_ptr()), _stream()))
+            M = int(count.item())
+            if M <= cap:
+                return pairs[:M]
+            cap = M
+
+    def trainset_gather(self, feats, rot, key):
+        """feats (nr,kn,32,60) f32 on the device, rot / key (B) host integer arrays -> (B,32,60) f32: out[b] = feats[rot[b], key[b]],
+        rows copied unchanged (yoho_trainset_gather; the indices are checked on the host and travel in kernel arguments)."""
+        if feats.dim() != 4 or tuple(feats.shape[2:]) != (32, 60):
+            raise ValueError("trainset_gather: feats (nr,kn,32,60)")
+        rot = np.ascontiguousarray(rot, dtype=np.int64).reshape(-1)
+        key = np.ascontiguousarray(key, dtype=np.int64).reshape(-1)
+        if rot.shape != key.shape:
+            raise ValueError("trainset_gather: rot and key must have one length")
+        B = rot.shape[0]
+        out = torch.empty((B, 32, 60), dtype=torch.float32, device=feats.device)
+        _check(self._lib.yoho_trainset_gather(self._h, _dev(feats, torch.float32, "feats"), feats.shape[0], feats.shape[1], _np_ptr(rot), _np_ptr(key), B,
+                                              C.c_void_p(out.data_ptr()), _stream()))
+        return out
 
     def mutual_nn(self, a, b):
         """a (Na,32), b (Nb,32) -> (M,2) int64 mutual nearest neighbours, ascending in a."""

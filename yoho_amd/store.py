@@ -12,6 +12,7 @@ import torch
 _store = {}
 _bytes = 0
 _stamp = {}            # path key -> (mtime_ns, size) of the file the resident tensor mirrors
+_extra = {}            # path key -> the small host arrays of an .npz whose large array is resident (load_npz)
 _cap = None
 
 
@@ -47,6 +48,7 @@ def put(key, tensor):
         _bytes -= v.numel() * v.element_size()
         del _store[k]
         _stamp.pop(k, None)
+        _extra.pop(k, None)
     _store[key] = tensor
     _bytes += nb
 
@@ -59,6 +61,7 @@ def clear():
     global _bytes
     _store.clear()
     _stamp.clear()
+    _extra.clear()
     _bytes = 0
 
 
@@ -74,6 +77,22 @@ def load_npy(path, dtype=torch.float32):
         put(key, t)
         _stamp[key] = _file_stamp(key)
     return t
+
+
+def load_npz(path, name, dtype=torch.float32):
+    """(device tensor of array `name` of an .npz stage file, {other array names: host arrays}): resident while the file on disk is the
+    one that was loaded (load_npy's rule); the small arrays stay on the host beside it"""
+    key = os.path.abspath(path)
+    t = get(key)
+    if t is None or key not in _extra or _stamp.get(key) != _file_stamp(key):
+        stamp = _file_stamp(key)
+        with np.load(key) as z:
+            extra = {k: z[k] for k in z.files if k != name}
+            t = torch.from_numpy(np.ascontiguousarray(z[name])).to(device="cuda", dtype=dtype)
+        put(key, t)
+        _stamp[key] = stamp
+        _extra[key] = extra
+    return t, _extra[key]
 
 
 def save_npy(path, tensor):

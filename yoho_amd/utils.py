@@ -72,3 +72,66 @@ def quaternion_from_matrix(matrix):
     if q[0] < 0.0:
         np.negative(q, q)
     return q
+
+
+def _about_z(t):
+    c, s = np.cos(t), np.sin(t)
+    return np.array([[c, s, 0], [-s, c, 0], [0, 0, 1]])
+
+
+def _about_y(t):
+    c, s = np.cos(t), np.sin(t)
+    return np.array([[c, 0, -s], [0, 1, 0], [s, 0, c]])
+
+
+def random_rotation_matrix(seed=None):
+    """utils/utils.py:52-83: a random axis (uniform in a cube, normalised) scaled by a random angle in [0, pi) gives three angles
+    (alpha, beta, gamma), R = Rz(gamma) Ry(beta) Rz(alpha).  Unseeded like the reference (a fresh np.random.RandomState() per call, so
+    the global np.random stream is not touched); `seed` makes the draw reproducible: RandomState(seed)."""
+    rng = np.random.RandomState(seed)
+    axis = rng.rand(3) - 0.5
+    axis /= np.linalg.norm(axis) + 1E-8
+    alpha, beta, gamma = axis * (np.pi * rng.uniform(0.0, 1.0))
+    return np.matmul(_about_z(gamma), np.matmul(_about_y(beta), _about_z(alpha)))
+
+
+def compute_R_diff(R_gt, R):
+    """utils/r_eval.py:112-120: the angle in degrees between two rotations from their quaternions, arccos(1 - 2 (1 - <q, q_gt>^2))"""
+    eps = 1e-15
+    q_gt, q = quaternion_from_matrix(R_gt), quaternion_from_matrix(R)
+    q = q / (np.linalg.norm(q) + eps)
+    q_gt = q_gt / (np.linalg.norm(q_gt) + eps)
+    loss_q = np.maximum(eps, (1.0 - np.sum(q * q_gt) ** 2))
+    return np.rad2deg(np.abs(np.arccos(1 - 2 * loss_q)))
+
+
+def quaternions_from_matrices(Ms):
+    """quaternion_from_matrix for a stack (n,3,3) -> (n,4): the same K matrices through one batched np.linalg.eigh (LAPACK solves
+    each 4x4 on its own, as the single call does)"""
+    M = np.asarray(Ms, dtype=np.float64)
+    K = np.zeros((M.shape[0], 4, 4))
+    K[:, 0, 0] = M[:, 0, 0] - M[:, 1, 1] - M[:, 2, 2]
+    K[:, 1, 0] = M[:, 0, 1] + M[:, 1, 0]
+    K[:, 1, 1] = M[:, 1, 1] - M[:, 0, 0] - M[:, 2, 2]
+    K[:, 2, 0] = M[:, 0, 2] + M[:, 2, 0]
+    K[:, 2, 1] = M[:, 1, 2] + M[:, 2, 1]
+    K[:, 2, 2] = M[:, 2, 2] - M[:, 0, 0] - M[:, 1, 1]
+    K[:, 3, 0] = M[:, 2, 1] - M[:, 1, 2]
+    K[:, 3, 1] = M[:, 0, 2] - M[:, 2, 0]
+    K[:, 3, 2] = M[:, 1, 0] - M[:, 0, 1]
+    K[:, 3, 3] = M[:, 0, 0] + M[:, 1, 1] + M[:, 2, 2]
+    K /= 3.0
+    w, V = np.linalg.eigh(K)
+    q = V[np.arange(M.shape[0])[:, None], [3, 0, 1, 2], np.argmax(w, axis=1)[:, None]]
+    q[q[:, 0] < 0.0] *= -1.0
+    return q
+
+
+def group_R_diff(Rgroup, Rs):
+    """compute_R_diff(Rgroup[g], Rs[n]) for every pair -> (n, len(Rgroup)) degrees, f64, vectorised"""
+    eps = 1e-15
+    qg, q = quaternions_from_matrices(Rgroup), quaternions_from_matrices(Rs)
+    qg = qg / (np.linalg.norm(qg, axis=1, keepdims=True) + eps)
+    q = q / (np.linalg.norm(q, axis=1, keepdims=True) + eps)
+    loss_q = np.maximum(eps, 1.0 - np.sum(q[:, None, :] * qg[None, :, :], axis=-1) ** 2)
+    return np.rad2deg(np.abs(np.arccos(1 - 2 * loss_q)))
