@@ -668,12 +668,15 @@ static int partI_pass16(yoho_ctx* c, const float* x, int B, float* eqv, float* i
     const size_t szX = (size_t)nT * 4 * chunk, szA = (size_t)nT * 32 * chunk, szA1 = (size_t)nT * 64 * chunk;
     const size_t szH0 = (size_t)nT * 32 * rawslabs, szY = (size_t)nT * 8 * rawslabs;   // Y padded to 64 channels
     int rc;
-    if ((rc = ensure_ws(c, szX + szA + szA1 + szH0 + szY, s))) return rc;
-    char* bX = (char*)c->ws.p;
-    char* bA = bX + szX;
-    char* bA1 = bA + szA;
-    float* bH0 = (float*)(bA1 + szA1);
-    float* bY = (float*)((char*)bH0 + szH0);
+    char *bX = nullptr, *bA = nullptr, *bA1 = nullptr;
+    float *bH0 = nullptr, *bY = nullptr;
+    if ((rc = bind_ws(c, s, [&](Arena& ar) {
+            bX = ar.take<char>(szX);
+            bA = ar.take<char>(szA);
+            bA1 = ar.take<char>(szA1);
+            bH0 = ar.take<float>(szH0 / sizeof(float));
+            bY = ar.take<float>(szY / sizeof(float));
+        }))) return rc;
     const bool prof = c->profiling && c->ev_created;
     auto mark = [&](int i) { if (prof) (void)hipEventRecord(c->ev[i], s); };
     if (prof) { c->ev_chunks = 1; (void)hipEventRecord(c->ev_pass[0], s); }
@@ -700,14 +703,16 @@ static int partI_passF(yoho_ctx* c, const float* x, int B, float* eqv, float* in
     const int nT = (B + TILE - 1) / TILE;
     const size_t nX = (size_t)nT * 4, n256 = (size_t)nT * 32, n512 = (size_t)nT * 64;
     int rc;
-    if ((rc = ensure_ws(c, (nX * 4 + n256 * 2 + n512) * CHUNK_FLOATS * sizeof(float), s))) return rc;
-    float* bS = (float*)c->ws.p;                  // packed input, group domain
-    float* bX = bS + nX * CHUNK_FLOATS;           // its Fourier coefficients
-    float* bH0 = bX + nX * CHUNK_FLOATS;          // raw h0 (Fourier), kept for the residual
-    float* bA = bH0 + n256 * CHUNK_FLOATS;        // act(h0), later h2 / act(h2)
-    float* bM = bA + n256 * CHUNK_FLOATS;         // mid 512 (in place raw -> act)
-    float* bY = bM + n512 * CHUNK_FLOATS;         // conv_out raw (Fourier)
-    float* bYs = bY + nX * CHUNK_FLOATS;          // conv_out raw (group domain)
+    float *bS = nullptr, *bX = nullptr, *bH0 = nullptr, *bA = nullptr, *bM = nullptr, *bY = nullptr, *bYs = nullptr;
+    if ((rc = bind_ws(c, s, [&](Arena& ar) {
+            bS = ar.take<float>(nX * CHUNK_FLOATS);       // packed input, group domain
+            bX = ar.take<float>(nX * CHUNK_FLOATS);       // its Fourier coefficients
+            bH0 = ar.take<float>(n256 * CHUNK_FLOATS);    // raw h0 (Fourier), kept for the residual
+            bA = ar.take<float>(n256 * CHUNK_FLOATS);     // act(h0), later h2 / act(h2)
+            bM = ar.take<float>(n512 * CHUNK_FLOATS);     // mid 512 (in place raw -> act)
+            bY = ar.take<float>(nX * CHUNK_FLOATS);       // conv_out raw (Fourier)
+            bYs = ar.take<float>(nX * CHUNK_FLOATS);      // conv_out raw (group domain)
+        }))) return rc;
     const bool prof = c->profiling && c->ev_created;
     auto mark = [&](int i) { if (prof) (void)hipEventRecord(c->ev[i], s); };
     const Layer* L = c->p1;
@@ -739,35 +744,47 @@ static int partI_passF(yoho_ctx* c, const float* x, int B, float* eqv, float* in
 }
 
 // group-Fourier variant: all four layers as irrep GEMMs on the fp16x2 split MFMA, fp16x2 transform kernels between them
-static size_t partI_G_ws_bytes(int B) {
+struct PartIGBufs {
+    float *bH0, *bA, *bM, *bY, *bYs;
+    char *bP32, *bP256, *bP512;
+};
+static void partI_G_layout(Arena& ar, int B, PartIGBufs& b) {
     const int nT = (B + TILE - 1) / TILE;
     const int kppad = (B + 255) / 256 * 256;
     const size_t nX = (size_t)nT * 4, n256 = (size_t)nT * 32, n512 = (size_t)nT * 64;
-    const size_t sz = (nX * 2 + n256 * 2 + n512) * CHUNK_FLOATS * sizeof(float) + fgemm_planes_bytes(kppad, 32) + fgemm_planes_bytes(kppad, 256) +
-                      fgemm_planes_bytes(kppad, 512);
-    return (sz + 4095) / 4096 * 4096;
+    b.bH0 = ar.take<float>(n256 * CHUNK_FLOATS);                  // raw h0 (Fourier), kept for the residual
+    b.bA = ar.take<float>(n256 * CHUNK_FLOATS);                   // raw h2
+    b.bM = ar.take<float>(n512 * CHUNK_FLOATS);                   // raw mid 512
+    b.bY = ar.take<float>(nX * CHUNK_FLOATS);                     // conv_out raw (Fourier)
+    b.bYs = ar.take<float>(nX * CHUNK_FLOATS);                    // conv_out raw (group domain), (B,32,60)
+    b.bP32 = ar.take<char>(fgemm_planes_bytes(kppad, 32));        // input coefficients as GEMM operand planes
+    b.bP256 = ar.take<char>(fgemm_planes_bytes(kppad, 256));      // act(h0), later act(h2)
+    b.bP512 = ar.take<char>(fgemm_planes_bytes(kppad, 512));      // act(mid)
+}
+// bytes of one chunk's workspace slice (the measuring run of its layout, in whole pages)
+static size_t partI_G_ws_bytes(int B) {
+    Arena measure;
+    PartIGBufs b;
+    partI_G_layout(measure, B, b);
+    return (measure.off + 4095) / 4096 * 4096;
 }
 
-// one chunk of the pass: B keypoints through head -> 4 GEMMs + 3 transforms -> tail on the workspace slice at `ws`; rows >= B0 of
-// the chunk come from x1 (when set).  evbase: first of this chunk's EV_PER_PASS profiling events.
-static int partI_passG_chunk(yoho_ctx* c, char* ws, int evbase, const float* x, int B, float* eqv, float* inv, float* inv_np, hipStream_t s,
+// one chunk of the pass: B keypoints through head -> 4 GEMMs + 3 transforms -> tail on the workspace slice of `slice` bytes at `ws`;
+// rows >= B0 of the chunk come from x1 (when set).  evbase: first of this chunk's EV_PER_PASS profiling events.
+static int partI_passG_chunk(yoho_ctx* c, char* ws, size_t slice, int evbase, const float* x, int B, float* eqv, float* inv, float* inv_np, hipStream_t s,
                              const float* x1, int B0, int slot) {
     // GEMM blocking: mode 4 = 256 x 256 tile, eight waves (two per SIMD) sharing the A stage | mode 5 = 256 x 256, four waves (one per SIMD) |
     // mode 6 = 256 x 128 tiles, two four-wave workgroups per CU.  The transform kernel follows: two waves per SIMD except in mode 5.
     const int gv = c->gconv_mode == 5 ? 1 : (c->gconv_mode == 6 ? 2 : 3);
     const int nT = (B + TILE - 1) / TILE;
     const int kppad = (B + 255) / 256 * 256;
-    const size_t nX = (size_t)nT * 4, n256 = (size_t)nT * 32, n512 = (size_t)nT * 64;
-    const size_t szP32 = fgemm_planes_bytes(kppad, 32), szP256 = fgemm_planes_bytes(kppad, 256);
     int rc;
-    float* bH0 = (float*)ws;                      // raw h0 (Fourier), kept for the residual
-    float* bA = bH0 + n256 * CHUNK_FLOATS;        // raw h2
-    float* bM = bA + n256 * CHUNK_FLOATS;         // raw mid 512
-    float* bY = bM + n512 * CHUNK_FLOATS;         // conv_out raw (Fourier)
-    float* bYs = bY + nX * CHUNK_FLOATS;          // conv_out raw (group domain), (B,32,60)
-    char* bP32 = (char*)(bYs + nX * CHUNK_FLOATS);    // input coefficients as GEMM operand planes
-    char* bP256 = bP32 + szP32;                       // act(h0), later act(h2)
-    char* bP512 = bP256 + szP256;                     // act(mid)
+    Arena ar{ws, 0, slice};
+    PartIGBufs b;
+    partI_G_layout(ar, B, b);
+    if (ar.over) { set_error("internal: PartI chunk of %d keypoints does not fit its workspace slice of %zu bytes", B, slice); return YOHO_EINVAL; }
+    float *bH0 = b.bH0, *bA = b.bA, *bM = b.bM, *bY = b.bY, *bYs = b.bYs;
+    char *bP32 = b.bP32, *bP256 = b.bP256, *bP512 = b.bP512;
     const bool prof = c->profiling && c->ev_created;
     auto mark = [&](int i) { if (prof) (void)hipEventRecord(c->ev[evbase + i], s); };
     const Layer* L = c->p1;
@@ -846,7 +863,7 @@ static int partI_passG(yoho_ctx* c, const float* x, int B, float* eqv, float* in
         const bool on_side = nstr == 2 && ((k & 1) || dbg_side);
         hipStream_t sk = on_side ? c->side_stream : s;
         char* ws = (char*)c->ws.p + (dbg_own ? slice * (size_t)k : (on_side ? slice : 0));
-        if ((rc = partI_passG_chunk(c, ws, k * EV_PER_PASS, xc, n, eqv + (size_t)off * F * G, inv ? inv + (size_t)off * F : nullptr,
+        if ((rc = partI_passG_chunk(c, ws, slice, k * EV_PER_PASS, xc, n, eqv + (size_t)off * F * G, inv ? inv + (size_t)off * F : nullptr,
                                     inv_np ? inv_np + (size_t)off * F : nullptr, sk, x1c, B0c, on_side ? 1 : 0))) break;
         if (dbg_serial && hipStreamSynchronize(sk) != hipSuccess) { set_error("hipStreamSynchronize failed"); rc = YOHO_EHIP; break; }
     }
@@ -866,15 +883,16 @@ static int partI_pass(yoho_ctx* c, const float* x, int B, float* eqv, float* inv
     if (c->gconv_mode == 1 || c->gconv_mode == 3) return partI_pass16(c, x, B, eqv, inv, inv_np, s, c->gconv_mode == 1 ? 3 : 2);
     if (c->gconv_mode == 2) return partI_passF(c, x, B, eqv, inv, inv_np, s);
     const int nT = (B + TILE - 1) / TILE;
-    const size_t ch = (size_t)CHUNK_FLOATS * sizeof(float);
     const size_t nX = (size_t)nT * 4, n256 = (size_t)nT * 32, n512 = (size_t)nT * 64;
     int rc;
-    if ((rc = ensure_ws(c, (nX * 2 + n256 * 2 + n512) * ch, s))) return rc;
-    float* bX = (float*)c->ws.p;
-    float* bH0 = bX + nX * CHUNK_FLOATS;
-    float* bA = bH0 + n256 * CHUNK_FLOATS;        // a0, later a2
-    float* bA1 = bA + n256 * CHUNK_FLOATS;
-    float* bY = bA1 + n512 * CHUNK_FLOATS;
+    float *bX = nullptr, *bH0 = nullptr, *bA = nullptr, *bA1 = nullptr, *bY = nullptr;
+    if ((rc = bind_ws(c, s, [&](Arena& ar) {
+            bX = ar.take<float>(nX * CHUNK_FLOATS);
+            bH0 = ar.take<float>(n256 * CHUNK_FLOATS);
+            bA = ar.take<float>(n256 * CHUNK_FLOATS);     // a0, later a2
+            bA1 = ar.take<float>(n512 * CHUNK_FLOATS);
+            bY = ar.take<float>(nX * CHUNK_FLOATS);
+        }))) return rc;
     const bool prof = c->profiling && c->ev_created;
     auto mark = [&](int i) { if (prof) (void)hipEventRecord(c->ev[i], s); };
     if (prof) { c->ev_chunks = 1; (void)hipEventRecord(c->ev_pass[0], s); }
@@ -928,7 +946,7 @@ static bool partII_fourier_head(const yoho_ctx* c) {
 static int partII_pass16(yoho_ctx* c, const float* s0, const float* s1, const float* s2, const float* s3, const int64_t* idx,
                          int M, float* quat, hipStream_t s, int npl, const int64_t* const* ridx = nullptr, int istride = 1) {
     const int nT16 = (M + 15) / 16, nT = (M + TILE - 1) / TILE;
-    const size_t ch = (size_t)CHUNK_FLOATS * sizeof(float), ch16 = (size_t)npl * 15360;
+    const size_t ch16 = (size_t)npl * 15360;
     const size_t n128 = (size_t)nT * 16, n256 = (size_t)nT * 32, n512 = (size_t)nT * 64, n32 = (size_t)nT * 4;
     // (PartII modes 3 / 4 keep the cone GEMM's stage blocks where the direct kernels keep their 256-channel planes: whole 256-match column tiles)
     const size_t szG = c->partII_mode >= 3 ? (size_t)((nT + 7) / 8) * c->cone_nslot * 8 * 32768 : 0;
@@ -936,28 +954,29 @@ static int partII_pass16(yoho_ctx* c, const float* s0, const float* s1, const fl
     const size_t szA1p = npl == 2 ? (size_t)nT16 * 64 * ch16 : 0;      // fp16x2: 13-cone activation planes for cone1_kernel
     int rc;
     int* rf = c->d_rflag + 1;                           // PartII's range word
-    if ((rc = ensure_ws(c, szX + szA0 + szA1p + (n256 + n512 + n256 + n512 + n128 + n32) * ch, s))) return rc;
-    char* bX = (char*)c->ws.p;                          // 128 ch planes
-    char* bA0 = bX + szX;                               // 256 ch planes (45 slabs valid)
-    char* bA1p = bA0 + szA0;                            // 512 ch planes (13 slabs valid)
-    float* bH0 = (float*)(bA1p + szA1p);                // 256 raw fp32, 32-tile layout
-    float* bA1 = bH0 + n256 * CHUNK_FLOATS;             // 512 act fp32 (13 slabs valid)
-    float* bF = bA1 + n512 * CHUNK_FLOATS;              // 256 raw (g = 0)
-    float* bF0 = bF + n256 * CHUNK_FLOATS;              // 512 act
-    float* bF1 = bF0 + n512 * CHUNK_FLOATS;             // 128 act
-    float* bQ = bF1 + n128 * CHUNK_FLOATS;              // 32 raw (4 used)
     if (ridx && !partII_fourier_head(c)) { set_error("indexed PartII needs the default (fp16x2, Fourier first layer) mode"); return YOHO_EINVAL; }
-    if (npl == 2 && partII_fourier_head(c)) {
+    const bool fourier_head = npl == 2 && partII_fourier_head(c);
+    const int kppad = (M + 255) / 256 * 256;
+    char *bX = nullptr, *bA0 = nullptr, *bA1p = nullptr, *bP = nullptr;
+    float *bH0 = nullptr, *bA1 = nullptr, *bF = nullptr, *bF0 = nullptr, *bF1 = nullptr, *bQ = nullptr, *bC = nullptr;
+    if ((rc = bind_ws(c, s, [&](Arena& ar) {
+            bX = ar.take<char>(szX);                            // 128 ch planes
+            bA0 = ar.take<char>(szA0);                          // 256 ch planes (45 slabs valid)
+            bA1p = ar.take<char>(szA1p);                        // 512 ch planes (13 slabs valid)
+            bH0 = ar.take<float>(n256 * CHUNK_FLOATS);          // 256 raw fp32, 32-tile layout
+            bA1 = ar.take<float>(n512 * CHUNK_FLOATS);          // 512 act fp32 (13 slabs valid)
+            bF = ar.take<float>(n256 * CHUNK_FLOATS);           // 256 raw (g = 0)
+            bF0 = ar.take<float>(n512 * CHUNK_FLOATS);          // 512 act
+            bF1 = ar.take<float>(n128 * CHUNK_FLOATS);          // 128 act
+            bQ = ar.take<float>(n32 * CHUNK_FLOATS);            // 32 raw (4 used)
+            if (fourier_head) {
+                bP = ar.take<char>(fgemm_planes_bytes(kppad, 128));      // the gathered input as GEMM operand planes
+                bC = ar.take<float>(n256 * CHUNK_FLOATS);                // raw Fourier coefficients of the first layer
+            }
+        }))) return rc;
+    if (fourier_head) {
         // first layer (128 -> 256) in the group-Fourier domain: all 60 outputs cost 244/780 of a full direct layer, i.e.
         // less than half of the 45-element cone the direct kernel computes
-        const int kppad = (M + 255) / 256 * 256;
-        const size_t szP = fgemm_planes_bytes(kppad, 128);
-        if ((rc = ensure_ws(c, szX + szA0 + szA1p + (n256 + n512 + n256 + n512 + n128 + n32) * ch + szP + n256 * ch, s))) return rc;
-        // ensure_ws may have moved the workspace
-        bX = (char*)c->ws.p; bA0 = bX + szX; bA1p = bA0 + szA0; bH0 = (float*)(bA1p + szA1p); bA1 = bH0 + n256 * CHUNK_FLOATS;
-        bF = bA1 + n512 * CHUNK_FLOATS; bF0 = bF + n256 * CHUNK_FLOATS; bF1 = bF0 + n512 * CHUNK_FLOATS; bQ = bF1 + n128 * CHUNK_FLOATS;
-        char* bP = (char*)(bQ + n32 * CHUNK_FLOATS);
-        float* bC = (float*)(bP + szP);                 // raw Fourier coefficients of the first layer
         if ((rc = launch_head2(s0, s1, s2, s3, idx, c->dP, c->p2_init_bn_s, c->p2_init_bn_t, M, nT, bP, kppad, c->dF16, s, ridx, istride, rf))) return rc;
         if ((rc = launch_fgemm(c->p2[0], bP, kppad, nT, nullptr, bC, 0, s, rf, c->env.partII_l1_variant))) return rc;
         if (c->partII_mode >= 3 && c->p2[1].wcg && !c->env.partII_tail_staged && mlp_head_supported(c->p2[3], c->p2[4], c->p2[5])) {
@@ -1008,18 +1027,19 @@ static int partII_pass(yoho_ctx* c, const float* s0, const float* s1, const floa
                        int M, float* quat, hipStream_t s) {
     if (c->partII_mode != 0) return partII_pass16(c, s0, s1, s2, s3, idx, M, quat, s, c->partII_mode == 1 ? 3 : 2);      // modes 2, 3, 4: two planes
     const int nT = (M + TILE - 1) / TILE;
-    const size_t ch = (size_t)CHUNK_FLOATS * sizeof(float);
     const size_t n128 = (size_t)nT * 16, n256 = (size_t)nT * 32, n512 = (size_t)nT * 64, n32 = (size_t)nT * 4;
     int rc;
-    if ((rc = ensure_ws(c, (n128 + 3 * n256 + 2 * n512 + n128 + n32) * ch, s))) return rc;
-    float* bX = (float*)c->ws.p;                       // 128 ch
-    float* bH0 = bX + n128 * CHUNK_FLOATS;             // 256 raw
-    float* bA0 = bH0 + n256 * CHUNK_FLOATS;            // 256 act
-    float* bA1 = bA0 + n256 * CHUNK_FLOATS;            // 512 act
-    float* bF = bA1 + n512 * CHUNK_FLOATS;             // 256 raw (g = 0)
-    float* bF0 = bF + n256 * CHUNK_FLOATS;             // 512 act
-    float* bF1 = bF0 + n512 * CHUNK_FLOATS;            // 128 act
-    float* bQ = bF1 + n128 * CHUNK_FLOATS;             // 32 raw (4 used)
+    float *bX = nullptr, *bH0 = nullptr, *bA0 = nullptr, *bA1 = nullptr, *bF = nullptr, *bF0 = nullptr, *bF1 = nullptr, *bQ = nullptr;
+    if ((rc = bind_ws(c, s, [&](Arena& ar) {
+            bX = ar.take<float>(n128 * CHUNK_FLOATS);           // 128 ch
+            bH0 = ar.take<float>(n256 * CHUNK_FLOATS);          // 256 raw
+            bA0 = ar.take<float>(n256 * CHUNK_FLOATS);          // 256 act
+            bA1 = ar.take<float>(n512 * CHUNK_FLOATS);          // 512 act
+            bF = ar.take<float>(n256 * CHUNK_FLOATS);           // 256 raw (g = 0)
+            bF0 = ar.take<float>(n512 * CHUNK_FLOATS);          // 512 act
+            bF1 = ar.take<float>(n128 * CHUNK_FLOATS);          // 128 act
+            bQ = ar.take<float>(n32 * CHUNK_FLOATS);            // 32 raw (4 used)
+        }))) return rc;
     if ((rc = launch_pack_partII(s0, s1, s2, s3, idx, c->dP, c->p2_init_bn_s, c->p2_init_bn_t, M, nT, bX, s))) return rc;
     // Only group element 0 of the last feature map is consumed (utils/network.py:273-276), so the
     // convs run on its receptive cone: 45 -> 13 -> 1 group elements.
@@ -1152,8 +1172,9 @@ int yoho_group_transfer_batch(yoho_ctx* c, const double* pts, const int64_t* kid
         HIPCHK(hipSetDevice(c->device));
         int mmax = 1;
         for (int b = 0; b < nb; ++b) mmax = m[b] > mmax ? m[b] : mmax;
-        if ((rc = ensure_ws(c, grid_transfer_ws_bytes(K, nb, mmax), (hipStream_t)stream))) return rc;
-        rc = launch_grid_transfer_batch(pts, kidx, K, R_host, nb, ds, feat, m, g0, out, c->nn_cell, c->ws.p, c->nCU, (hipStream_t)stream);
+        GridWs w;
+        if ((rc = bind_ws(c, (hipStream_t)stream, [&](Arena& ar) { grid_transfer_layout(ar, K, nb, mmax, w); }))) return rc;
+        rc = launch_grid_transfer_batch(pts, kidx, K, R_host, nb, ds, feat, m, g0, out, c->nn_cell, w, c->nCU, (hipStream_t)stream);
         phase_mark(c, -1, (hipStream_t)stream);
         return rc;
     }

@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <initializer_list>
 #include "yoho_hip.h"
+#include "arena.h"
 
 namespace yoho {
 
@@ -188,20 +189,41 @@ int launch_pack_partII(const float* s0, const float* s1, const float* s2, const 
                        const int* P, const float* bn_s, const float* bn_t, int M, int nTiles, float* out, hipStream_t s);
 int launch_quat_norm(const float* y, int M, float* quat, hipStream_t s);
 
-size_t mutual_prefilter_ws_bytes(int Na, int Nb);
-int launch_mutual_prefilter(const float* a, int Na, const float* b, int Nb, void* ws, unsigned long long** keysA, unsigned long long** keysB,
-                            int nCU, hipStream_t s, int nn_splits = 0);
-size_t grid_transfer_ws_bytes(int K, int nb, int mmax);
+// scratch of the mutual-NN pre-filter (matchf.hip), and what its kernels are launched with
+struct MfArgs {
+    const float* a; const float* b;
+    int Na, Nb;
+    float* na2; float* nb2;              // squared norms
+    _Float16* a16; _Float16* b16;        // the rows rounded to fp16 (RNE), 32 halfs each: the MFMA operands of both Gram passes
+    unsigned* rowmin; unsigned* colmin;  // ordered-integer images of the minima of s (per a row) and t (per b row)
+    unsigned long long* keysA; unsigned long long* keysB;   // packed (distance bits << 32 | index) winners
+    unsigned* maxn2;                     // [0] max |a_i|^2 bits, [1] max |b_j|^2 bits
+    int* bad;                            // non-finite / out-of-range input: brute force instead
+    int tilesPer;                        // 32-row tiles of the OTHER set per workgroup of the Gram passes
+    unsigned long long* cand;            // pass 2: candidate pairs (i << 34 | j << 4 | for_row << 1 | for_col), evaluated exactly by mf_exact_kernel
+    unsigned* ncand; unsigned cap;       // their number (may exceed cap: then `bad` is raised and brute force answers)
+};
+void mutual_prefilter_layout(Arena& ar, int Na, int Nb, MfArgs& p);
+// p: bound by mutual_prefilter_layout; p.keysA (Na) / p.keysB (Nb) receive the packed winners (the layout launch_mutual_compact<PACKED> reads)
+int launch_mutual_prefilter(MfArgs& p, const float* a, const float* b, int nCU, hipStream_t s, int nn_splits = 0);
+// scratch of the hash-grid searches (gridnn.hip): one open-addressing table of `cap` cells per copy, the chains of the target points
+// and the list of queries the grid could not resolve
+struct GridWs {
+    unsigned long long* keys; int* head; unsigned cap;
+    int* next; int* ulist; int* ucount;
+};
+void grid_nn_layout(Arena& ar, int Ns, int Nt, GridWs& w);
+void grid_transfer_layout(Arena& ar, int K, int nb, int mmax, GridWs& w);      // copy b: keys / head + b * cap, next + b * mmax, ulist + b * K, ucount[b]
 int launch_grid_transfer_batch(const double* pts, const int64_t* kidx, int K, const double* R_host, int nb, const float* const* ds,
-                               const float* const* feat, const int* m, int g0, float* out, double cell, void* ws, int nCU, hipStream_t s);
+                               const float* const* feat, const int* m, int g0, float* out, double cell, const GridWs& w, int nCU, hipStream_t s);
 struct Workspace;
 }  // namespace yoho
 struct yoho_ctx;
 namespace yoho {
 int ensure_ws(yoho_ctx* ctx, size_t bytes, hipStream_t s);
 struct GnMat3;
-size_t grid_nn_ws_bytes(int Ns, int Nt);
-int launch_grid_nn(int mode, const void* src, int Ns, const GnMat3* R, const float* tgt, int Nt, double cell, void* ws, int64_t* idx, float* dist,
+// w: bound by grid_nn_layout(Ns, Nt).  mode 0/1: idx/dist outputs; mode 2: part_d/part_i (Ns entries each).
+int launch_grid_nn(int mode, const void* src, int Ns, const GnMat3* R, const float* tgt, int Nt, double cell, const GridWs& w, int64_t* idx, float* dist,
                    double* part_d, int* part_i, int nCU, hipStream_t s);
 
 struct Workspace {
@@ -344,3 +366,24 @@ inline void phase_work(yoho_ctx* c, int cat, double flops) {
 }
 }  // namespace yoho
 namespace yoho { constexpr int EV_PER_PASS = 11; }
+
+namespace yoho {
+// The one way a pass gets its scratch (arena.h): lay(Arena&) takes the pass's buffers.  It is run on a measuring arena, the context
+// workspace is grown to what it took (ensure_ws, once: growing frees the old block, so no pointer may exist before), and it is run
+// again on that block with the measured bytes - not the grown allocation - as its bound, so a take the two runs disagree on fails here.
+template <typename Lay>
+int bind_ws(yoho_ctx* ctx, hipStream_t s, Lay&& lay) {
+    Arena measure;
+    lay(measure);
+    if (measure.over) { set_error("internal: workspace layout overflows size_t"); return YOHO_EINVAL; }
+    int rc;
+    if ((rc = ensure_ws(ctx, measure.off, s))) return rc;
+    Arena bound{(char*)ctx->ws.p, 0, measure.off};
+    lay(bound);
+    if (bound.over || bound.off != measure.off) {
+        set_error("internal: workspace layout took %zu bytes when bound, %zu when measured", bound.off, measure.off);
+        return YOHO_EINVAL;
+    }
+    return 0;
+}
+}  // namespace yoho

@@ -589,8 +589,7 @@ int yoho_o_score(yoho_ctx* c, const double* k0, const double* k1, int M, const d
     int rc;
     int32_t* cnt = counts;
     if (!cnt) {
-        if ((rc = ensure_ws(c, sizeof(int32_t) * (size_t)H, s))) return rc;
-        cnt = (int32_t*)c->ws.p;
+        if ((rc = bind_ws(c, s, [&](Arena& ar) { cnt = ar.take<int32_t>((size_t)H); }))) return rc;
     }
     hipLaunchKernelGGL(score_kernel, dim3(H), dim3(256), 0, s, k0, k1, M, T, order, d * d, cnt);
     HIPCHK(hipGetLastError());
@@ -609,12 +608,15 @@ int yoho_c_ransac(yoho_ctx* c, const double* k0, const double* k1, int M, const 
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    // workspace: T (I,12) f64 | counts (I) i32 | best_h i32
-    const size_t need = sizeof(double) * 12 * (size_t)I + sizeof(int32_t) * ((size_t)I + 4);
-    if ((rc = ensure_ws(c, need, s))) return rc;
-    double* Tall = T_out ? T_out : (double*)c->ws.p;
-    int32_t* cnt = counts ? counts : (int32_t*)((char*)c->ws.p + sizeof(double) * 12 * (size_t)I);
-    int* bh = (int*)((char*)c->ws.p + sizeof(double) * 12 * (size_t)I + sizeof(int32_t) * (size_t)I);
+    // workspace: best_h, and the hypotheses and their counts where the caller does not want them
+    double* Tall = T_out;
+    int32_t* cnt = counts;
+    int* bh = nullptr;
+    if ((rc = bind_ws(c, s, [&](Arena& ar) {
+            if (!T_out) Tall = ar.take<double>(12 * (size_t)I);
+            if (!counts) cnt = ar.take<int32_t>((size_t)I);
+            bh = ar.take<int>(4);
+        }))) return rc;
     hipLaunchKernelGGL(kabsch_score_kernel, dim3(I), dim3(256), 0, s, k0, k1, M, triples, reflect, d * d, Tall, cnt);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(argbest_kernel, dim3(1), dim3(256), 0, s, cnt, I, bh, best_count);
@@ -636,20 +638,21 @@ int yoho_c_ransac_device(yoho_ctx* c, const double* keys0, const int64_t* i0, co
     hipStream_t s = (hipStream_t)stream;
     int rc;
     const size_t I = (size_t)max_iter;
-    // workspace: T (I,12) f64 | matched keys 2 x (M,3) f64 | CStat | counts (I) i32 | members (M) i32 | best_h
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
-    const size_t oT = take(sizeof(double) * 12 * I), oK0 = take(sizeof(double) * 3 * (size_t)M), oK1 = take(sizeof(double) * 3 * (size_t)M);
-    const size_t oS = take(sizeof(CStat)), oC = take(sizeof(int32_t) * I), oM = take(sizeof(int) * (size_t)M), oB = take(16), oD = take((size_t)M);
-    if ((rc = ensure_ws(c, off, s))) return rc;
-    char* w = (char*)c->ws.p;
-    double* Tall = (double*)(w + oT);
-    double *k0m = (double*)(w + oK0), *k1m = (double*)(w + oK1);
-    CStat* st = (CStat*)(w + oS);
-    int32_t* cnt = (int32_t*)(w + oC);
-    int* members = (int*)(w + oM);
-    int* bh = (int*)(w + oB);
-    unsigned char* dr8 = (unsigned char*)(w + oD);
+    double *Tall = nullptr, *k0m = nullptr, *k1m = nullptr;     // hypotheses (I,12), matched keys 2 x (M,3)
+    CStat* st = nullptr;
+    int32_t* cnt = nullptr;
+    int *members = nullptr, *bh = nullptr;
+    unsigned char* dr8 = nullptr;
+    if ((rc = bind_ws(c, s, [&](Arena& ar) {
+            Tall = ar.take<double>(12 * I);
+            k0m = ar.take<double>(3 * (size_t)M);
+            k1m = ar.take<double>(3 * (size_t)M);
+            st = ar.take<CStat>(1);
+            cnt = ar.take<int32_t>(I);
+            members = ar.take<int>((size_t)M);
+            bh = ar.take<int>(4);
+            dr8 = ar.take<unsigned char>((size_t)M);
+        }))) return rc;
     hipLaunchKernelGGL(cprep_kernel, dim3((M + 255) / 256), dim3(256), 0, s, dr_index, M, keys0, keys1, i0, i1, istride, dr8, k0m, k1m);
     hipLaunchKernelGGL(cstat_kernel, dim3(1), dim3(64 * CS_WAVES), 0, s, dr8, M, st, members);
     HIPCHK(hipGetLastError());
@@ -678,11 +681,15 @@ int yoho_group_gather(yoho_ctx* c, const double* keys, int K, const float* pts, 
     if (c->nn_cell > 0.0 && (size_t)K * n >= (1u << 20)) {
         // hash-grid search (gridnn.hip): same winners as the brute-force slices below
         int rc;
-        const size_t head = ((size_t)K * (sizeof(double) + sizeof(int)) + 255) & ~(size_t)255;
-        if ((rc = ensure_ws(c, head + grid_nn_ws_bytes(K, n), s))) return rc;
-        double* pd = (double*)c->ws.p;
-        int* pi = (int*)(pd + K);
-        if ((rc = launch_grid_nn(2, keys, K, &R, pts, n, c->nn_cell, (char*)c->ws.p + head, nullptr, nullptr, pd, pi, c->nCU, s))) return rc;
+        double* pd = nullptr;
+        int* pi = nullptr;
+        GridWs w;
+        if ((rc = bind_ws(c, s, [&](Arena& ar) {
+                pd = ar.take<double>((size_t)K);
+                pi = ar.take<int>((size_t)K);
+                grid_nn_layout(ar, K, n, w);
+            }))) return rc;
+        if ((rc = launch_grid_nn(2, keys, K, &R, pts, n, c->nn_cell, w, nullptr, nullptr, pd, pi, c->nCU, s))) return rc;
         hipLaunchKernelGGL(gather_merge_kernel, dim3((K + 15) / 16), dim3(256), 0, s, pd, pi, K, 1, feat, g, out, nn_idx);
         HIPCHK(hipGetLastError());
         return 0;
@@ -695,9 +702,9 @@ int yoho_group_gather(yoho_ctx* c, const double* keys, int K, const float* pts, 
     const int slice_len = ((n + nslice - 1) / nslice + 255) / 256 * 256;
     nslice = (n + slice_len - 1) / slice_len;
     int rc;
-    if ((rc = ensure_ws(c, (size_t)nslice * K * (sizeof(double) + sizeof(int)), s))) return rc;
-    double* pd = (double*)c->ws.p;
-    int* pi = (int*)(pd + (size_t)nslice * K);
+    double* pd = nullptr;
+    int* pi = nullptr;
+    if ((rc = bind_ws(c, s, [&](Arena& ar) { pd = ar.take<double>((size_t)nslice * K); pi = ar.take<int>((size_t)nslice * K); }))) return rc;
     hipLaunchKernelGGL(gather_nn_kernel, dim3(kblocks, nslice), dim3(256), 0, s, keys, K, pts, n, R, slice_len, pd, pi);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(gather_merge_kernel, dim3((K + 15) / 16), dim3(256), 0, s, pd, pi, K, nslice, feat, g, out, nn_idx);

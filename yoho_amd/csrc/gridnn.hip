@@ -176,24 +176,28 @@ __global__ __launch_bounds__(256) void gn_fallback_kernel(GnArgs a) {
     }
 }
 
-size_t grid_nn_ws_bytes(int Ns, int Nt) {
+static unsigned grid_cells(int n) {           // power of two, at least twice the points
     unsigned cap = 1024;
-    while (cap < 2u * (unsigned)Nt) cap <<= 1;
-    return (size_t)cap * 12 + ((size_t)Nt + Ns) * 4 + 256;
+    while (cap < 2u * (unsigned)n) cap <<= 1;
+    return cap;
 }
 
-// ws: grid_nn_ws_bytes(Ns, Nt) bytes of scratch.  mode 0/1: idx/dist outputs; mode 2: part_d/part_i (Ns entries each).
-int launch_grid_nn(int mode, const void* src, int Ns, const GnMat3* R, const float* tgt, int Nt, double cell, void* ws, int64_t* idx, float* dist,
+void grid_nn_layout(Arena& ar, int Ns, int Nt, GridWs& w) {
+    w.cap = grid_cells(Nt);
+    w.keys = ar.take<u64>(w.cap);
+    w.head = ar.take<int>(w.cap);
+    w.next = ar.take<int>((size_t)Nt);
+    w.ulist = ar.take<int>((size_t)Ns);
+    w.ucount = ar.take<int>(1);
+}
+
+int launch_grid_nn(int mode, const void* src, int Ns, const GnMat3* R, const float* tgt, int Nt, double cell, const GridWs& w, int64_t* idx, float* dist,
                    double* part_d, int* part_i, int nCU, hipStream_t s) {
-    unsigned cap = 1024;
-    while (cap < 2u * (unsigned)Nt) cap <<= 1;
-    char* p = (char*)ws;
+    const unsigned cap = w.cap;
+    u64* keys = w.keys;
+    int *head = w.head, *next = w.next;
     GnArgs a;
-    u64* keys = (u64*)p; p += (size_t)cap * 8;
-    int* head = (int*)p; p += (size_t)cap * 4;
-    int* next = (int*)p; p += (size_t)Nt * 4;
-    a.ulist = (int*)p; p += (size_t)Ns * 4;
-    a.ucount = (int*)p;
+    a.ulist = w.ulist; a.ucount = w.ucount;
     a.src = src; a.Ns = Ns; a.tgt = tgt; a.Nt = Nt;
     if (R) a.R = *R; else for (int i = 0; i < 9; ++i) a.R.m[i] = i % 4 == 0 ? 1.0 : 0.0;
     a.inv_cell = 1.0 / cell; a.lim2 = 4.0 * cell * cell * (1.0 - 1e-4);
@@ -338,25 +342,23 @@ __global__ __launch_bounds__(256) void gt_fallback_kernel(GtBatch a) {
     }
 }
 
-size_t grid_transfer_ws_bytes(int K, int nb, int mmax) {
-    unsigned cap = 1024;
-    while (cap < 2u * (unsigned)mmax) cap <<= 1;
-    return ((size_t)cap * 12 + ((size_t)mmax + K) * 4) * nb + 1024;
+void grid_transfer_layout(Arena& ar, int K, int nb, int mmax, GridWs& w) {
+    w.cap = grid_cells(mmax);
+    w.keys = ar.take<u64>((size_t)w.cap * nb);
+    w.head = ar.take<int>((size_t)w.cap * nb);
+    w.next = ar.take<int>((size_t)mmax * nb);
+    w.ulist = ar.take<int>((size_t)K * nb);
+    w.ucount = ar.take<int>((size_t)nb);
 }
 
-// nb <= 64 copies (launched GT_BATCH at a time); ws: grid_transfer_ws_bytes(K, nb, max m) bytes
+// nb <= 64 copies (launched GT_BATCH at a time); w: bound by grid_transfer_layout(K, nb, max m)
 int launch_grid_transfer_batch(const double* pts, const int64_t* kidx, int K, const double* R_host, int nb, const float* const* ds,
-                               const float* const* feat, const int* m, int g0, float* out, double cell, void* ws, int nCU, hipStream_t s) {
+                               const float* const* feat, const int* m, int g0, float* out, double cell, const GridWs& w, int nCU, hipStream_t s) {
     int mmax = 1;
     for (int b = 0; b < nb; ++b) mmax = m[b] > mmax ? m[b] : mmax;
-    unsigned cap = 1024;
-    while (cap < 2u * (unsigned)mmax) cap <<= 1;
-    char* p = (char*)ws;
-    u64* keys = (u64*)p; p += (size_t)cap * 8 * nb;
-    int* head = (int*)p; p += (size_t)cap * 4 * nb;
-    int* next = (int*)p; p += (size_t)mmax * 4 * nb;
-    int* ulist = (int*)p; p += (size_t)K * 4 * nb;
-    int* ucount = (int*)p;
+    const unsigned cap = w.cap;
+    u64* keys = w.keys;
+    int *head = w.head, *next = w.next, *ulist = w.ulist, *ucount = w.ucount;
     {
         const size_t total = (size_t)cap * nb;
         hipLaunchKernelGGL(gt_clear_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, keys, head, total, ucount, nb);

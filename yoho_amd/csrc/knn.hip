@@ -226,8 +226,7 @@ int yoho_knn_search(yoho_ctx* c, const float* src, int Ns, const float* tgt, int
     unsigned long long* keys = nullptr;
     if (nseg > 1) {
         int rc;
-        if ((rc = ensure_ws(c, sizeof(unsigned long long) * (size_t)Ns * nseg * k, s))) return rc;
-        keys = (unsigned long long*)c->ws.p;
+        if ((rc = bind_ws(c, s, [&](Arena& ar) { keys = ar.take<unsigned long long>((size_t)Ns * nseg * k); }))) return rc;
     }
     const dim3 grid((Ns + KNN_ROWS - 1) / KNN_ROWS, nseg);
     if (D == 32 && !sq) knn_launch<32, false>(grid, s, src, Ns, tgt, Nt, k, segLen, keys, idx, dist);

@@ -358,14 +358,15 @@ int yoho_nn_search(yoho_ctx* c, const float* src, int Ns, const float* tgt, int 
     HIPCHK(hipSetDevice(c->device));
     if (D == 3 && c->nn_cell > 0.0 && (size_t)Ns * Nt >= (1u << 20) && (dist_type == YOHO_DIST_L2 || dist_type == YOHO_DIST_SQUARE_L2)) {
         int rc;
-        if ((rc = ensure_ws(c, grid_nn_ws_bytes(Ns, Nt), (hipStream_t)stream))) return rc;
-        return launch_grid_nn(dist_type == YOHO_DIST_SQUARE_L2 ? 0 : 1, src, Ns, nullptr, tgt, Nt, c->nn_cell, c->ws.p, idx, dist, nullptr, nullptr,
+        GridWs w;
+        if ((rc = bind_ws(c, (hipStream_t)stream, [&](Arena& ar) { grid_nn_layout(ar, Ns, Nt, w); }))) return rc;
+        return launch_grid_nn(dist_type == YOHO_DIST_SQUARE_L2 ? 0 : 1, src, Ns, nullptr, tgt, Nt, c->nn_cell, w, idx, dist, nullptr, nullptr,
                               c->nCU, (hipStream_t)stream);
     }
     if ((D == 32 || D == 3) && (size_t)Ns * Nt >= (1u << 20) && (dist_type == YOHO_DIST_L2 || dist_type == YOHO_DIST_SQUARE_L2)) {
         int rc;
-        if ((rc = ensure_ws(c, sizeof(unsigned long long) * (size_t)Ns, (hipStream_t)stream))) return rc;
-        unsigned long long* keys = (unsigned long long*)c->ws.p;
+        unsigned long long* keys = nullptr;
+        if ((rc = bind_ws(c, (hipStream_t)stream, [&](Arena& ar) { keys = ar.take<unsigned long long>((size_t)Ns); }))) return rc;
         if ((rc = launch_nn32seg(src, Ns, tgt, Nt, dist_type == YOHO_DIST_SQUARE_L2, keys, c->nCU, (hipStream_t)stream, D))) return rc;
         return launch_nn_unpack(keys, Ns, idx, dist, (hipStream_t)stream);
     }
@@ -378,19 +379,16 @@ int yoho_mutual_nn(yoho_ctx* c, const float* a, int Na, const float* b, int Nb, 
     YOHO_NEED_ALIGNED("yoho_mutual_nn", 3, M_out);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    // workspace: fwd (Na) + back (Nb) int64, placed after everything the descriptor passes use
-    const size_t need = sizeof(int64_t) * ((size_t)Na + Nb);
     int rc;
-    if ((rc = ensure_ws(c, need, s))) return rc;
-    int64_t* fwd = (int64_t*)c->ws.p;
-    int64_t* back = fwd + Na;
     if ((size_t)Na * Nb >= (1u << 20) && c->nn_prefilter) {
         // MFMA pre-filter + exact evaluation of the candidates (matchf.hip): the same packed keys as the segmented search below
-        if ((rc = ensure_ws(c, mutual_prefilter_ws_bytes(Na, Nb), s))) return rc;
-        unsigned long long *kA = nullptr, *kB = nullptr;
-        if ((rc = launch_mutual_prefilter(a, Na, b, Nb, c->ws.p, &kA, &kB, c->nCU, s, c->env.nn_splits))) return rc;
-        return launch_mutual_compact((const int64_t*)kA, (const int64_t*)kB, Na, pairs, M_out, s, true);
+        MfArgs p;
+        if ((rc = bind_ws(c, s, [&](Arena& ar) { mutual_prefilter_layout(ar, Na, Nb, p); }))) return rc;
+        if ((rc = launch_mutual_prefilter(p, a, b, c->nCU, s, c->env.nn_splits))) return rc;
+        return launch_mutual_compact((const int64_t*)p.keysA, (const int64_t*)p.keysB, Na, pairs, M_out, s, true);
     }
+    int64_t *fwd = nullptr, *back = nullptr;                    // nearest neighbour of every a row in b, of every b row in a
+    if ((rc = bind_ws(c, s, [&](Arena& ar) { fwd = ar.take<int64_t>((size_t)Na); back = ar.take<int64_t>((size_t)Nb); }))) return rc;
     if ((size_t)Na * Nb >= (1u << 20)) {
         // segmented search: the workspace words are the packed keys, the compaction reads the index half
         if ((rc = launch_nn32seg(a, Na, b, Nb, false, (unsigned long long*)fwd, c->nCU, s))) return rc;

@@ -29,20 +29,6 @@ namespace yoho {
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef _Float16 halfx8 __attribute__((ext_vector_type(8)));
 
-struct MfArgs {
-    const float* a; const float* b;
-    int Na, Nb;
-    float* na2; float* nb2;              // squared norms
-    _Float16* a16; _Float16* b16;        // the rows rounded to fp16 (RNE), 32 halfs each: the MFMA operands of both Gram passes
-    unsigned* rowmin; unsigned* colmin;  // ordered-integer images of the minima of s (per a row) and t (per b row)
-    unsigned long long* keysA; unsigned long long* keysB;   // packed (distance bits << 32 | index) winners
-    unsigned* maxn2;                     // [0] max |a_i|^2 bits, [1] max |b_j|^2 bits
-    int* bad;                            // non-finite / out-of-range input: brute force instead
-    int tilesPer;                        // 32-row tiles of the OTHER set per workgroup of the Gram passes
-    unsigned long long* cand;            // pass 2: candidate pairs (i << 34 | j << 4 | for_row << 1 | for_col), evaluated exactly by mf_exact_kernel
-    unsigned* ncand; unsigned cap;       // their number (may exceed cap: then `bad` is raised and brute force answers)
-};
-
 __device__ __forceinline__ unsigned ord_of(float f) {          // monotone map float -> unsigned
     const unsigned u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -264,32 +250,25 @@ __global__ __launch_bounds__(256) void mf_gram_kernel(MfArgs p) {
 
 int launch_nn32seg_if(const float* src, int Ns, const float* tgt, int Nt, unsigned long long* keys, int nCU, const int* run_if, hipStream_t s);
 
-size_t mutual_prefilter_ws_bytes(int Na, int Nb) {
-    const size_t n = (size_t)Na + Nb;
-    return n * (sizeof(unsigned long long) + sizeof(float) + sizeof(unsigned) + 64) + 512 + (32 * n + 4096) * sizeof(unsigned long long);
+void mutual_prefilter_layout(Arena& ar, int Na, int Nb, MfArgs& p) {
+    p.Na = Na; p.Nb = Nb;
+    p.keysA = ar.take<unsigned long long>((size_t)Na);
+    p.keysB = ar.take<unsigned long long>((size_t)Nb);
+    p.na2 = ar.take<float>((size_t)Na);
+    p.nb2 = ar.take<float>((size_t)Nb);
+    p.rowmin = ar.take<unsigned>((size_t)Na);
+    p.colmin = ar.take<unsigned>((size_t)Nb);
+    p.maxn2 = ar.take<unsigned>(4);                            // four words cleared together: the two maxima, `bad`, the candidate count
+    p.a16 = ar.take<_Float16>(32 * (size_t)Na);
+    p.b16 = ar.take<_Float16>(32 * (size_t)Nb);
+    p.cap = 32u * (unsigned)(Na + Nb) + 4000u;                 // a pair in the band of both its row and its column is listed once per direction
+    p.cand = ar.take<unsigned long long>(p.cap);
 }
 
-// keysA (Na) / keysB (Nb) receive the packed winners (the layout launch_mutual_compact<PACKED> reads); ws as sized above
-int launch_mutual_prefilter(const float* a, int Na, const float* b, int Nb, void* ws, unsigned long long** keysA, unsigned long long** keysB,
-                            int nCU, hipStream_t s, int nn_splits) {
-    MfArgs p;
-    char* w = (char*)ws;
-    p.a = a; p.b = b; p.Na = Na; p.Nb = Nb;
-    p.keysA = (unsigned long long*)w; w += sizeof(unsigned long long) * (size_t)Na;
-    p.keysB = (unsigned long long*)w; w += sizeof(unsigned long long) * (size_t)Nb;
-    p.na2 = (float*)w; w += sizeof(float) * (size_t)Na;
-    p.nb2 = (float*)w; w += sizeof(float) * (size_t)Nb;
-    p.rowmin = (unsigned*)w; w += sizeof(unsigned) * (size_t)Na;
-    p.colmin = (unsigned*)w; w += sizeof(unsigned) * (size_t)Nb;
-    p.maxn2 = (unsigned*)w; w += 2 * sizeof(unsigned);
-    p.bad = (int*)w; w += sizeof(int);
-    p.ncand = (unsigned*)w; w += sizeof(unsigned);
-    w = (char*)(((size_t)w + 63) & ~(size_t)63);
-    p.a16 = (_Float16*)w; w += 64 * (size_t)Na;
-    p.b16 = (_Float16*)w; w += 64 * (size_t)Nb;
-    p.cand = (unsigned long long*)(((size_t)w + 15) & ~(size_t)15);
-    p.cap = 32u * (unsigned)(Na + Nb) + 4000u;                 // a pair in the band of both its row and its column is listed once per direction
-    *keysA = p.keysA; *keysB = p.keysB;
+int launch_mutual_prefilter(MfArgs& p, const float* a, const float* b, int nCU, hipStream_t s, int nn_splits) {
+    const int Na = p.Na, Nb = p.Nb;
+    p.a = a; p.b = b;
+    p.bad = (int*)(p.maxn2 + 2); p.ncand = p.maxn2 + 3;
     HIPCHK(hipMemsetAsync(p.maxn2, 0, 16, s));                  // maxima, `bad`, candidate count
     const int n = Na + Nb;
     hipLaunchKernelGGL(mf_norms_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p);

@@ -166,23 +166,36 @@ struct PairScratch {
     PairDev* out;
 };
 
+static void pair_layout(Arena& ar, size_t N, PairScratch& p) {
+    p.pairs = ar.take<int64_t>(2 * N); p.dr = ar.take<int64_t>(N); p.order = ar.take<int64_t>(N); p.ms = ar.take<int64_t>(2 * N);
+    p.drs = ar.take<int64_t>(N); p.k0m = ar.take<double>(3 * N); p.k1m = ar.take<double>(3 * N); p.k0s = ar.take<double>(3 * N);
+    p.k1s = ar.take<double>(3 * N); p.T = ar.take<double>(12 * N); p.bestT = ar.take<double>(12); p.quat = ar.take<float>(4 * N);
+    p.res = ar.take<int>(4); p.out = ar.take<PairDev>(1);
+}
+
+// the arena rule of bind_ws on the context's pair scratch (its own allocation: it outlives the staged calls' use of the workspace)
 static int pair_scratch(yoho_ctx* c, int n, PairScratch& p, hipStream_t s) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
     const size_t N = (size_t)n;
-    const size_t o_pairs = take(16 * N), o_dr = take(8 * N), o_order = take(8 * N), o_ms = take(16 * N), o_drs = take(8 * N);
-    const size_t o_k0m = take(24 * N), o_k1m = take(24 * N), o_k0s = take(24 * N), o_k1s = take(24 * N), o_T = take(96 * N), o_bT = take(96);
-    const size_t o_q = take(16 * N), o_res = take(16), o_out = take(sizeof(PairDev));
-    if (c->pair_ws_bytes < off) {
+    Arena measure;
+    pair_layout(measure, N, p);
+    if (measure.over) { set_error("internal: pair scratch layout overflows size_t"); return YOHO_EINVAL; }
+    const size_t need = measure.off;                       // (a multiple of 4: every buffer holds 4- or 8-byte words)
+    if (c->pair_ws_bytes < need) {
         if (c->pair_ws) {
             HIPCHK(hipStreamSynchronize(s));
             HIPCHK(hipFree(c->pair_ws));
             c->pair_ws = nullptr; c->pair_ws_bytes = 0;
         }
-        hipError_t e = hipMalloc(&c->pair_ws, off);
-        if (e != hipSuccess) { set_error("pair scratch of %zu bytes: %s", off, hipGetErrorString(e)); return YOHO_ENOMEM; }
-        c->pair_ws_bytes = off;
-        if (c->poison) HIPCHK(hipMemsetD32Async(c->pair_ws, (int)c->poison_pattern, off / 4, s));
+        hipError_t e = hipMalloc(&c->pair_ws, need);
+        if (e != hipSuccess) { set_error("pair scratch of %zu bytes: %s", need, hipGetErrorString(e)); return YOHO_ENOMEM; }
+        c->pair_ws_bytes = need;
+        if (c->poison) HIPCHK(hipMemsetD32Async(c->pair_ws, (int)c->poison_pattern, need / 4, s));
+    }
+    Arena bound{(char*)c->pair_ws, 0, measure.off};
+    pair_layout(bound, N, p);
+    if (bound.over || bound.off != measure.off) {
+        set_error("internal: pair scratch layout took %zu bytes when bound, %zu when measured", bound.off, measure.off);
+        return YOHO_EINVAL;
     }
     const size_t host_need = 8 * N + 256;
     if (c->pair_host_bytes < host_need) {
@@ -191,11 +204,6 @@ static int pair_scratch(yoho_ctx* c, int n, PairScratch& p, hipStream_t s) {
         if (e != hipSuccess) { set_error("pinned pair scratch of %zu bytes: %s", host_need, hipGetErrorString(e)); return YOHO_ENOMEM; }
         c->pair_host_bytes = host_need;
     }
-    char* w = (char*)c->pair_ws;
-    p.pairs = (int64_t*)(w + o_pairs); p.dr = (int64_t*)(w + o_dr); p.order = (int64_t*)(w + o_order); p.ms = (int64_t*)(w + o_ms);
-    p.drs = (int64_t*)(w + o_drs); p.k0m = (double*)(w + o_k0m); p.k1m = (double*)(w + o_k1m); p.k0s = (double*)(w + o_k0s);
-    p.k1s = (double*)(w + o_k1s); p.T = (double*)(w + o_T); p.bestT = (double*)(w + o_bT); p.quat = (float*)(w + o_q);
-    p.res = (int*)(w + o_res); p.out = (PairDev*)(w + o_out);
     return 0;
 }
 

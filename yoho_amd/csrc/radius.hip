@@ -170,9 +170,9 @@ int yoho_radius_pairs(yoho_ctx* c, const float* a, int Na, const float* b, int N
         return 0;
     }
     int rc;
-    if ((rc = ensure_ws(c, (sizeof(int64_t) + sizeof(int)) * (size_t)Na, s))) return rc;
-    int64_t* rowoff = (int64_t*)c->ws.p;
-    int* rowcount = (int*)(rowoff + Na);
+    int64_t* rowoff = nullptr;
+    int* rowcount = nullptr;
+    if ((rc = bind_ws(c, s, [&](Arena& ar) { rowoff = ar.take<int64_t>((size_t)Na); rowcount = ar.take<int>((size_t)Na); }))) return rc;
     const RadiusTest t = radius_test(radius);
     const dim3 grid((Na + RP_WAVES - 1) / RP_WAVES), block(64 * RP_WAVES);
     hipLaunchKernelGGL((radius_kernel<false>), grid, block, 0, s, a, Na, b, Nb, t, rowcount, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0);

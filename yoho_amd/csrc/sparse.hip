@@ -1906,16 +1906,14 @@ static unsigned table_cap(int n) {
     return c;
 }
 
-// bump allocator over the context workspace
-struct Arena {
-    char* p; size_t off = 0, cap;
-    template <typename Tp> Tp* take(size_t cnt) {
-        off = (off + 255) & ~(size_t)255;
-        Tp* r = reinterpret_cast<Tp*>(p + off);
-        off += cnt * sizeof(Tp);
-        return r;
-    }
-};
+// The passes of this file size their workspace from estimates (fcgf_workspace_bytes, the voxelisations' formulas): how much they take
+// depends on counts that come back in the middle of a pass, so they cannot measure first as bind_ws does.  Instead every group of takes
+// is checked before the first launch that uses a pointer of the group.  An overrun is a defect of the estimate, not an exhausted
+// device: YOHO_EINVAL, so that the recoveries that retry on YOHO_ENOMEM do not hide it.
+static int arena_overrun(const Arena& ar, const char* what) {
+    set_error("internal: workspace estimate too small at %s: %zu > %zu", what, ar.off, ar.cap);
+    return YOHO_EINVAL;
+}
 
 static int build_table(const CoordSrc& src, int n, Level& L, hipStream_t s) {
     const unsigned cap = L.mask + 1;
@@ -1977,6 +1975,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
     L[0].n = n0; L[0].ts = 1; L[0].coords = ar.take<int>((size_t)n0 * 4);
     int* dbb = ar.take<int>(64 * 6);
     int* dbbpart = ar.take<int>(7 * 1100);               // per-workgroup partial boxes of bbox_kernel (<= 1024 + nb <= 1088 runs)
+    if (ar.over) return arena_overrun(ar, "fcgf_forward: level-0 rows");
     // <= 1024 + nb workgroups, each a run of rows of one cloud
     CloudOff ho;
     ho.off[0] = 0; ho.off[1] = n0;
@@ -2072,7 +2071,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
             }
             ddesc = reinterpret_cast<BmDesc*>(ar.take<char>(sizeof(BmDesc) * 64));
             operm = ar.take<int>((size_t)n0);
-            if (ar.off > ar.cap) ok = false;
+            if (ar.over) ok = false;
         }
         if (ok) {
             for (int b = 0; b < nb; ++b) hdesc[b] = BmDesc{hrk[0][b].base, hrk[0][b].x0, hrk[0][b].y0, hrk[0][b].z0, hrk[0][b].wx, hrk[0][b].ny, hrk[0][b].nz};
@@ -2113,7 +2112,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
                 HIPCHK(hipGetLastError());
             }
         }
-        if (!rank_mode) { ar.off = mark; operm = nullptr; ddesc = nullptr; }
+        if (!rank_mode) { ar.off = mark; ar.over = false; operm = nullptr; ddesc = nullptr; }      // (nothing was over at `mark`: checked above)
     }
     if (!rank_mode && (ctx->fcgf_cell_sort > 1 || (ctx->fcgf_cell_sort == 1 && n0 >= CELL_SORT_MIN_ROWS))) {
         const int ncell = nb * CELL_PER_CLOUD, nblk = ncell / 1024;
@@ -2121,7 +2120,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
         int* btot = ar.take<int>(nblk + 1);
         int* sorted = ar.take<int>((size_t)n0 * 4);
         operm = ar.take<int>((size_t)n0);
-        if (ar.off > ar.cap) { set_error("fcgf_forward: workspace estimate too small"); return YOHO_ENOMEM; }
+        if (ar.over) return arena_overrun(ar, "fcgf_forward: cell sort");
         HIPCHK(hipMemsetAsync(cnt, 0, sizeof(int) * 2 * (size_t)ncell, s));
         hipLaunchKernelGGL(cell_count_kernel, dim3((n0 + 255) / 256), dim3(256), 0, s, L[0].coords, n0, cnt);
         hipLaunchKernelGGL(cell_scan_kernel, dim3(nblk), dim3(1024), 0, s, cnt, btot);
@@ -2141,6 +2140,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
             L[l].mask = table_cap(nprev) - 1;
             L[l].keys = ar.take<u64>(L[l].mask + 1);
             L[l].vals = ar.take<int>(L[l].mask + 1);
+            if (ar.over) return arena_overrun(ar, "fcgf_forward: hash tables");
             if (l == 0) {
                 CoordSrc src{L[0].coords, nullptr, 1.0, 1, 0, {0}, nullptr, dcount};
                 if ((rc = build_table(src, n0, L[0], s))) return rc;
@@ -2150,6 +2150,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
                 if ((rc = build_table(src, nprev, L[l], s))) return rc;
                 L[l].coords = ar.take<int>((size_t)nprev * 4);
                 int* bsum = ar.take<int>((size_t)(nprev + 1023) / 1024 + 1);
+                if (ar.over) return arena_overrun(ar, "fcgf_forward: coarse rows");
                 if ((rc = launch_first_compact(src, nprev, L[l].keys, L[l].vals, L[l].mask, bsum, L[l].coords, 4, nullptr, dcount + l, s))) return rc;
                 int hd[2] = {0, 0};
                 HIPCHK(hipMemcpyAsync(hd, dcount + l - 1, sizeof(int) * 2, hipMemcpyDeviceToHost, s));      // l = 1: [duplicate flag, n1]
@@ -2170,6 +2171,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
     auto make_map = [&](const Level& outL, const Level& inL, int ksize, int ts, int sign) -> int* {
         const int kv = ksize * ksize * ksize;
         int* m = ar.take<int>((size_t)kv * outL.n);
+        if (ar.over) return m;                                 // null, nothing launched: the caller checks the arena
         const bool filter = map_bm && inL.ts == 1;             // the bitmap holds the level-0 voxels
         const int li = (int)(&inL - L);                        // level that is looked up
         if (outL.n > 0 && rank_mode)
@@ -2182,6 +2184,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
         return m;
     };
     int* M1 = conv1_fused ? nullptr : make_map(L[0], L[0], net->k1, 1, +1);
+    if (ar.over) return arena_overrun(ar, "fcgf_forward: first kernel map");
     // occupancy bitmaps for the first convolution (skipped if a cloud's bounding box is too large: hash probes then); the rank
     // path has them already
     if (conv1_fused && !rank_mode) {
@@ -2208,6 +2211,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
             dbm_words = words;
             dbm = ar.take<unsigned>((size_t)words + 2);            // + spare words: conv1_mfma_kernel reads word pairs
             ddesc = reinterpret_cast<BmDesc*>(ar.take<char>(sizeof(BmDesc) * 64));
+            if (ar.over) return arena_overrun(ar, "fcgf_forward: occupancy bitmaps");
             HIPCHK(hipMemsetAsync(dbm, 0, ((size_t)words + 2) * 4, s));
             HIPCHK(hipMemcpyAsync(ddesc, hdesc, sizeof(BmDesc) * nb, hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(bitmap_fill_kernel, dim3((n0 + 255) / 256), dim3(256), 0, s, L[0].coords, n0, ddesc, dbm);
@@ -2220,10 +2224,10 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
     // build and the inverted maps are only ever written for the FIRST row of a voxel
     const bool full_maps = ctx->env.fcgf_full_maps || has_dups;
     for (int l = 0; l < 4; ++l) {
-        if (full_maps) { Msame[l] = make_map(L[l], L[l], 3, L[l].ts, +1); continue; }
         // symmetric 3^3 map: offsets 0..12 looked up, 14..26 mirrored, 13 = identity (build_map_sym_kernel)
-        Msame[l] = ar.take<int>((size_t)27 * L[l].n);
-        if (ar.off > ar.cap) { set_error("fcgf_forward: workspace estimate too small"); return YOHO_ENOMEM; }
+        Msame[l] = full_maps ? make_map(L[l], L[l], 3, L[l].ts, +1) : ar.take<int>((size_t)27 * L[l].n);
+        if (ar.over) return arena_overrun(ar, "fcgf_forward: same-level kernel maps");
+        if (full_maps) continue;
         if (L[l].n == 0) continue;
         HIPCHK(hipMemsetAsync(Msame[l] + (size_t)14 * L[l].n, 0xFF, sizeof(int) * (size_t)13 * L[l].n, s));
         const bool filter = map_bm && L[l].ts == 1;
@@ -2236,10 +2240,11 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
     }
     for (int l = 0; l < 3; ++l) {
         Mdown[l] = make_map(L[l + 1], L[l], 3, L[l].ts, +1);           // strided conv: offsets on the input (finer) stride
-        if (full_maps) { Mup[l] = make_map(L[l], L[l + 1], 3, L[l].ts, -1); continue; }     // transposed: coarse row at coord(fine) - offset
-        // ... which is the strided map with input and output exchanged (invert_map_kernel): no second probe pass
-        Mup[l] = ar.take<int>((size_t)27 * L[l].n);
-        if (ar.off > ar.cap) { set_error("fcgf_forward: workspace estimate too small"); return YOHO_ENOMEM; }
+        // transposed: coarse row at coord(fine) - offset ... which is the strided map with input and output exchanged
+        // (invert_map_kernel): no second probe pass
+        Mup[l] = full_maps ? make_map(L[l], L[l + 1], 3, L[l].ts, -1) : ar.take<int>((size_t)27 * L[l].n);
+        if (ar.over) return arena_overrun(ar, "fcgf_forward: strided kernel maps");
+        if (full_maps) continue;
         if (L[l].n == 0) continue;
         HIPCHK(hipMemsetAsync(Mup[l], 0xFF, sizeof(int) * (size_t)27 * L[l].n, s));
         if (L[l + 1].n > 0)
@@ -2251,7 +2256,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
         nperm[l] = L[l].n + 8 * PAR_PAD;
         perm[l] = ar.take<int>((size_t)nperm[l]);
         int* pc = ar.take<int>(16);
-        if (ar.off > ar.cap) { set_error("fcgf_forward: workspace estimate too small"); return YOHO_ENOMEM; }
+        if (ar.over) return arena_overrun(ar, "fcgf_forward: parity orders");
         if (L[l].n == 0) continue;
         HIPCHK(hipMemsetAsync(perm[l], 0xFF, sizeof(int) * (size_t)nperm[l], s));
         HIPCHK(hipMemsetAsync(pc, 0, sizeof(int) * 16, s));
@@ -2261,6 +2266,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
     HIPCHK(hipGetLastError());
     // ---- features
     float* ones = ar.take<float>((size_t)n0 * net->in_ch);
+    if (ar.over) return arena_overrun(ar, "fcgf_forward: input features");
     hipLaunchKernelGGL(fill_ones_kernel, dim3((n0 * net->in_ch + 255) / 256), dim3(256), 0, s, ones, n0 * net->in_ch);
     float* x[4]; float* tmp[4]; float* cat[3]; float* enc3;
     const int catw[3] = {T[2] + C[1], T[3] + C[2], T[4] + C[3]}, catoff[3] = {T[2], T[3], T[4]};
@@ -2270,7 +2276,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
         if (l < 3) cat[l] = ar.take<float>((size_t)L[l].n * catw[l]);
     }
     enc3 = ar.take<float>((size_t)L[3].n * C[4]);
-    if (ar.off > ar.cap) { set_error("fcgf_forward: workspace estimate too small (%zu > %zu)", ar.off, ar.cap); return YOHO_ENOMEM; }
+    if (ar.over) return arena_overrun(ar, "fcgf_forward: encoder features");
 
     int conv_cat = -1;                          // phase category of the next conv() calls (yoho_phase_read)
     int conv_norm = 0;                          // > 0: the next conv() normalises its output rows in its epilogue (and hands them back in the caller's order)
@@ -2332,7 +2338,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
         const int co = j == 0 ? T[4] : (j == 1 ? T[3] : T[2]);
         float* u = ar.take<float>((size_t)L[l].n * co);
         float* sc = ar.take<float>((size_t)L[l].n * co);
-        if (ar.off > ar.cap) { set_error("fcgf_forward: workspace estimate too small"); return YOHO_ENOMEM; }
+        if (ar.over) return arena_overrun(ar, "fcgf_forward: decoder features");
         conv_cat = 11 + l;
         if ((rc = conv(din, dld, dcin, Mup[l], 27, L[l].n, net->conv_tr[j], co, u, co, 0, &net->norm_tr[j], nullptr, nullptr, 0, 0, 0,
                        ctx->fcgf_parity_sort ? perm[l] : nullptr, nperm[l]))) return rc;
@@ -2342,7 +2348,7 @@ static int fcgf_forward_attempt(yoho_ctx* ctx, const FcgfNet* net, const int* co
     }
     float* f1 = ar.take<float>((size_t)n0 * T[1]);
     float* f2 = ar.take<float>((size_t)n0 * net->out_ch);
-    if (ar.off > ar.cap) { set_error("fcgf_forward: workspace estimate too small"); return YOHO_ENOMEM; }
+    if (ar.over) return arena_overrun(ar, "fcgf_forward: head features");
     conv_cat = 14;
     // both heads in one launch where the fused kernel exists (96 -> 64 -> 32 channels, fp16x2 packs, a pass large enough for the fused
     // normalisation): the 64-channel intermediate never leaves the CU (YOHO_FCGF_HEADS=staged: the two launches below)
@@ -2422,11 +2428,12 @@ int fcgf_voxelize(yoho_ctx* ctx, const double* pts, int n, const double* R_host,
     Level L;
     L.mask = cap - 1; L.keys = ar.take<u64>(cap); L.vals = ar.take<int>(cap);
     int* dcount = ar.take<int>(2);                       // [0] number of voxels, [1] out-of-range flag
+    int* bsum = ar.take<int>((size_t)(n + 1023) / 1024 + 1);
+    if (ar.over) return arena_overrun(ar, "fcgf_voxelize");
     HIPCHK(hipMemsetAsync(dcount, 0, 2 * sizeof(int), s));
     CoordSrc src{nullptr, pts, voxel, 1, R_host ? 1 : 0, {0}, dcount + 1};
     if (R_host) for (int i = 0; i < 9; ++i) src.R[i] = R_host[i];
     if ((rc = build_table(src, n, L, s))) return rc;
-    int* bsum = ar.take<int>((size_t)(n + 1023) / 1024 + 1);
     if ((rc = launch_first_compact(src, n, L.keys, L.vals, L.mask, bsum, coords, 3, sel, dcount, s))) return rc;
     int hc[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(hc, dcount, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2456,10 +2463,13 @@ static int voxelize_batch_rank(yoho_ctx* ctx, const double* pts, int n, const do
     int rc;
     const int gblk = std::min(256, (n + 255) / 256);
     if ((rc = ensure_ws(ctx, 64 * 1024, s))) return rc;
+    Arena ar0{(char*)ctx->ws.p, 0, ctx->ws.bytes};
+    double* dpart = ar0.take<double>(6 * (size_t)gblk);    // per-workgroup partial bounds of the cloud
+    if (ar0.over) return arena_overrun(ar0, "fcgf_voxelize_batch: bounds");
     phase_mark(ctx, 0, s);
     double hpart[256 * 6];
-    hipLaunchKernelGGL(aabb_kernel, dim3(gblk), dim3(256), 0, s, pts, n, reinterpret_cast<double*>(ctx->ws.p));
-    HIPCHK(hipMemcpyAsync(hpart, ctx->ws.p, sizeof(double) * 6 * gblk, hipMemcpyDeviceToHost, s));
+    hipLaunchKernelGGL(aabb_kernel, dim3(gblk), dim3(256), 0, s, pts, n, dpart);
+    HIPCHK(hipMemcpyAsync(hpart, dpart, sizeof(double) * 6 * gblk, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     for (int g = 0; g < gblk; ++g)
@@ -2505,7 +2515,7 @@ static int voxelize_batch_rank(yoho_ctx* ctx, const double* pts, int n, const do
     int* btot = ar.take<int>((size_t)blocks + 2);
     int* first = ar.take<int>((size_t)nb * n);
     int* bsum = ar.take<int>(((size_t)nblk + 1) * nb);
-    if (ar.off > ar.cap) { set_error("fcgf_voxelize_batch: workspace estimate too small"); return YOHO_ENOMEM; }
+    if (ar.over) return arena_overrun(ar, "fcgf_voxelize_batch: rank arrays");
     HIPCHK(hipMemcpyAsync(dd, hd, sizeof(RkDesc) * nb, hipMemcpyHostToDevice, s));      // hd lives until the synchronisation below
     HIPCHK(hipMemsetAsync(dcount, 0, sizeof(int) * (2 * nb + 2), s));
     HIPCHK(hipMemsetAsync(bm, 0, ((size_t)words + 2) * 4, s));
@@ -2568,7 +2578,7 @@ int fcgf_voxelize_batch(yoho_ctx* ctx, const double* pts, int n, const double* R
     u64* keys = ar.take<u64>((size_t)cap * nb);
     int* vals = ar.take<int>((size_t)cap * nb);
     int* bsum = ar.take<int>(((size_t)nblk + 1) * nb);
-    if (ar.off > ar.cap) { set_error("fcgf_voxelize_batch: workspace estimate too small"); return YOHO_ENOMEM; }
+    if (ar.over) return arena_overrun(ar, "fcgf_voxelize_batch: hash tables");
     phase_mark(ctx, 0, s);
     HIPCHK(hipMemsetAsync(dcount, 0, 2 * sizeof(int) * nb, s));
     {

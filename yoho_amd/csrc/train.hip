@@ -238,11 +238,13 @@ int gconv_layer(yoho_ctx* c, const float* x, int B, int cin, int cout, const flo
     const size_t szX = (size_t)nT * (ecin / 8) * CHUNK_FLOATS, szY = (size_t)nT * (cpad / 8) * CHUNK_FLOATS;
     const size_t szW = (size_t)nob * (ecin / 8) * NTAP * 256;
     int rc;
-    if ((rc = ensure_ws(c, (szX + szY + szW + cpad64 + 64) * sizeof(float), s))) return rc;
-    float* bX = (float*)c->ws.p;
-    float* bY = bX + szX;
-    float* wp = bY + szY;
-    float* bb = wp + szW;
+    float *bX = nullptr, *bY = nullptr, *wp = nullptr, *bb = nullptr;      // packed input, raw output, packed weights, padded bias
+    if ((rc = bind_ws(c, s, [&](Arena& ar) {
+            bX = ar.take<float>(szX);
+            bY = ar.take<float>(szY);
+            wp = ar.take<float>(szW);
+            bb = ar.take<float>((size_t)cpad64);
+        }))) return rc;
     hipLaunchKernelGGL(pack_bcg_kernel, dim3(nT * (ecin / 8)), dim3(256), 0, s, x, B, ecin / 8, bX);
     hipLaunchKernelGGL(pack_w_dev_kernel, dim3((unsigned)((szW + 255) / 256)), dim3(256), 0, s, W, cin, cout, transpose, c->d_tap_inv, ecin, ecout,
                        nob, wp);
