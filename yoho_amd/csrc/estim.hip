@@ -63,18 +63,7 @@ __global__ __launch_bounds__(256) void hyp_kernel(const float* __restrict__ quat
     }
 }
 
-// inlier test of one match under one [R|t] (3x4 row-major)
-__device__ __forceinline__ bool inlier(const double* T, const double* a, const double* b, double d2thr) {
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const double p = __dadd_rn(fma(b[2], T[i * 4 + 2], fma(b[1], T[i * 4 + 1], b[0] * T[i * 4])), T[i * 4 + 3]);
-        const double e = __dsub_rn(a[i], p);
-        const double q = __dmul_rn(e, e);
-        s = i == 0 ? q : __dadd_rn(s, q);
-    }
-    return s < d2thr;
-}
+// inlier(): the inlier test of one match under one [R|t] lives in nnmath.h (refine.hip votes with the same function)
 
 __device__ __forceinline__ int block_count(bool flag_acc_unused, int local, int* red) {
     // sum `local` over a 256-thread workgroup

@@ -48,4 +48,18 @@ __device__ __forceinline__ double dist2_key_f64(const double* kr, double px, dou
     return __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
 }
 
+// inlier test of one match under one [R|t] (3x4 row-major): the vote of estim.hip and the refit of refine.hip (both built with
+// -ffp-contract=off: only the explicit fma() fuses)
+__device__ __forceinline__ bool inlier(const double* T, const double* a, const double* b, double d2thr) {
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double p = __dadd_rn(fma(b[2], T[i * 4 + 2], fma(b[1], T[i * 4 + 1], b[0] * T[i * 4])), T[i * 4 + 3]);
+        const double e = __dsub_rn(a[i], p);
+        const double q = __dmul_rn(e, e);
+        s = i == 0 ? q : __dadd_rn(s, q);
+    }
+    return s < d2thr;
+}
+
 }  // namespace yoho

@@ -329,8 +329,52 @@ class yohoo(_Base):
         R_pre_log(dataset, Save_dir)
 
 
+class yohoo_refit(yohoo):
+    """YOHO-O, then the winner refitted on its inlier matches (refine.refine_pair: iterated Kabsch on the device).  Not in the
+    reference.  ransac() first runs yohoo.ransac unchanged - same draws from np.random, same files under YOHO_O/ - and then writes
+    results of its own under YOHO_O_refit/: trans (the refitted 3 x 4; yohoo's where it found no inlier), recalltime as yohoo's,
+    inliers / inliers_pre (matches within the inlier distance after / before), counts (refine_pair's refit_counts), and a pre.log
+    through write_pre_log."""
+    refit_iters = 4
+    result_sign = 'YOHO_O_refit'          # the directory under Match/ whose pre.log the evaluator scores (RR_cal.benchmark's yoho_sign)
+
+    def ransac(self, dataset, max_iter=1000):
+        from .refine import refine_pair
+        super().ransac(dataset, max_iter)
+        match_dir = f'{self.cfg.output_cache_fn}/Testset/{dataset.name}/Match'
+        Pre_dir = f'{match_dir}/YOHO_O/{max_iter}iters'
+        Save_dir = f'{match_dir}/{self.result_sign}/{max_iter}iters'
+        make_non_exists_dir(Save_dir)
+        print(f'Refit of YOHO-O on {dataset.name}:')
+        for id0, id1 in dataset.pair_ids:
+            pre = np.load(f'{Pre_dir}/{id0}-{id1}.npz')
+            trans, recall = pre['trans'], int(pre['recalltime'])
+            pps = np.load(f'{match_dir}/{id0}-{id1}.npy')
+            counts = np.full((self.refit_iters + 1,), -1, dtype=np.int32)
+            n_pre = n_post = 0
+            if trans.shape[0] == 3 and len(pps):         # yohoo saves eye(4) where no hypothesis has an inlier
+                km0 = dataset.get_kps(id0)[pps[:, 0]]
+                km1 = dataset.get_kps(id1)[pps[:, 1]]
+                res = refine_pair(self.ctx, _cu(km0, np.float64), _cu(km1, np.float64), None, trans, self.inliner_dist, iters=self.refit_iters)
+                trans, counts = res['trans'], res['refit_counts']
+                n_pre, n_post = int(counts[0]), res['inliers']
+            np.savez(f'{Save_dir}/{id0}-{id1}.npz', trans=trans, recalltime=recall, inliers=n_post, inliers_pre=n_pre, counts=counts)
+        R_pre_log(dataset, Save_dir)
+
+
 name2estimator = {
     'yohoc': yohoc,
     'yohoc_mul': yohoc_mul,
     'yohoo': yohoo
 }
+# plug-ins beyond the reference's table: name2estimator keeps the reference's three keys (tests/test_gpu_dropin.py pins them), the
+# estimators this project adds are looked up here
+extra_estimators = {
+    'yohoo_refit': yohoo_refit
+}
+
+
+def get_estimator(name):
+    """the estimator class of a cfg.estimator name: the reference's table first, then this project's plug-ins (what
+    evaluator._Evaluator resolves cfg.estimator with, so cfg.estimator = 'yohoo_refit' selects the refit)"""
+    return name2estimator[name] if name in name2estimator else extra_estimators[name]

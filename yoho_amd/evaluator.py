@@ -15,7 +15,7 @@ from .dataset import get_dataset
 from .utils import transform_points, dataset_feature_name
 from .extractor import name2extractor, extractor_dr_index
 from .matcher import name2matcher
-from .estimator import name2estimator
+from .estimator import name2estimator, get_estimator  # noqa: F401  (name2estimator: the reference's table, re-exported as before)
 
 
 def match_inlier_ratio(keys0, keys1, matches, gt, dist_threshold):
@@ -32,7 +32,9 @@ class _Evaluator:
         self.extractor = name2extractor[cfg.extractor](cfg)
         self.matcher = name2matcher[cfg.matcher](cfg)
         self.drindex_extractor = extractor_dr_index(cfg)
-        self.estimator = name2estimator[self._estimator_name()](cfg)
+        self.estimator = get_estimator(self._estimator_name())(cfg)          # the reference's three names, then this project's plug-ins
+        # a plug-in that writes results of its own (estimator.yohoo_refit: Match/YOHO_O_refit) is scored on them
+        self.yoho_sign = getattr(self.estimator, "result_sign", self.yoho_sign)
 
     def _estimator_name(self):
         return self.cfg.estimator

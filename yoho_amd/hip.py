@@ -1,4 +1,4 @@
-"""ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h) + a thin tensor-level wrapper.
+"""ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h, include/yoho_refine.h) + a thin tensor-level wrapper.
 
 PyTorch-ROCm tensors are the device-memory container only: every method passes
 ``tensor.data_ptr()`` and the current HIP stream to the C ABI.  There is NO CPU fallback: if the
@@ -35,6 +35,12 @@ KNN_MAX = 16                                # YOHO_KNN_MAX
 # the entries of include/yoho_trainset.h (training-set generation), kept apart for the same reason
 TRAINSET_SYMBOLS = ["yoho_radius_pairs", "yoho_trainset_gather"]
 RADIUS_MAX_POINTS = 1 << 20                 # YOHO_RADIUS_MAX_POINTS
+# the entries of include/yoho_refine.h (refinement behind the estimators), kept apart for the same reason
+REFINE_SYMBOLS = ["yoho_nn_within", "yoho_refit_matches", "yoho_icp_refine"]
+REFINE_MAX_POINTS = 1 << 22                 # YOHO_REFINE_MAX_POINTS
+REFIT_MAX_ITERS = 32                        # YOHO_REFIT_MAX_ITERS
+ICP_MAX_ITERS = 64                          # YOHO_ICP_MAX_ITERS
+ICP_REASONS = ("iters", "converged", "few_pairs", "rank")      # YOHO_ICP_ITERS .. YOHO_ICP_RANK
 
 
 class ConvW(C.Structure):
@@ -80,7 +86,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -137,7 +143,10 @@ def load_library():
     lib.yoho_knn_search.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp]
     lib.yoho_radius_pairs.argtypes = [vp, vp, ci, vp, ci, C.c_float, vp, C.c_int64, vp, vp]
     lib.yoho_trainset_gather.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS:
+    lib.yoho_nn_within.argtypes = [vp, vp, ci, vp, ci, C.c_float, vp, vp, vp]
+    lib.yoho_refit_matches.argtypes = [vp, vp, vp, ci, vp, C.c_double, ci, vp, vp, vp, vp]
+    lib.yoho_icp_refine.argtypes = [vp, vp, ci, vp, ci, vp, C.c_float, ci, C.c_double, vp, vp, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -619,6 +628,51 @@ class Context:
         _check(self._lib.yoho_trainset_gather(self._h, _dev(feats, torch.float32, "feats"), feats.shape[0], feats.shape[1], _np_ptr(rot), _np_ptr(key), B,
                                               C.c_void_p(out.data_ptr()), _stream()))
         return out
+
+    # ---- refinement (include/yoho_refine.h) -------------------------------------------------
+    def nn_within(self, q, tgt, max_dist, want_d2=True):
+        """q (Nq,3), tgt (Nt,3) f32 -> (d2 (Nq) f32 or None, idx (Nq) int64): the nearest row of tgt strictly inside max_dist - nn_search's
+        D = 3 squared answer kept iff it is below the gate -, idx -1 / d2 +inf where there is none (yoho_nn_within)."""
+        if q.dim() != 2 or tgt.dim() != 2 or q.shape[1] != 3 or tgt.shape[1] != 3:
+            raise ValueError("nn_within: q (Nq,3), tgt (Nt,3)")
+        Nq, Nt = q.shape[0], tgt.shape[0]
+        idx = torch.empty((Nq,), dtype=torch.int64, device=q.device)
+        d2 = torch.empty((Nq,), dtype=torch.float32, device=q.device) if want_d2 else None
+        _check(self._lib.yoho_nn_within(self._h, _dev(q, torch.float32, "q"), Nq, _dev(tgt, torch.float32, "tgt"), Nt, float(max_dist),
+                                        C.c_void_p(idx.data_ptr()), C.c_void_p(d2.data_ptr()) if want_d2 else None, _stream()))
+        return d2, idx
+
+    def refit_matches(self, k0, k1, T, inlier_dist, iters=4):
+        """k0, k1 (M,3) f64 matched keypoints, T (3,4) f64 on the device (a winner of o_score / c_ransac chains in without a host read)
+        -> (T_out (3,4) f64, counts (iters + 1) int32, info int32[2] = (index of the iterate returned, iterates evaluated)), device
+        tensors: iterated Kabsch on the inlier matches, the iterate with the most inliers (yoho_refit_matches)."""
+        M, iters = k0.shape[0], int(iters)
+        if tuple(k0.shape) != (M, 3) or tuple(k1.shape) != (M, 3) or T.numel() != 12:
+            raise ValueError("refit_matches: k0, k1 (M,3), T (3,4)")
+        T_out = torch.empty((3, 4), dtype=torch.float64, device=T.device)
+        counts = torch.empty((max(iters, 0) + 1,), dtype=torch.int32, device=T.device)
+        info = torch.empty((2,), dtype=torch.int32, device=T.device)
+        _check(self._lib.yoho_refit_matches(self._h, _dev(k0, torch.float64, "k0") if M else None, _dev(k1, torch.float64, "k1") if M else None, M,
+                                            _dev(T, torch.float64, "T"), float(inlier_dist), iters, C.c_void_p(T_out.data_ptr()),
+                                            C.c_void_p(counts.data_ptr()), C.c_void_p(info.data_ptr()), _stream()))
+        return T_out, counts, info
+
+    def icp_refine(self, src, tgt, T, max_dist, iters=30, tol=0.0):
+        """src (Ns,3), tgt (Nt,3) f32 clouds, T (3,4) f64 on the device mapping src onto tgt -> (T_out (3,4) f64, npairs (iters) int32,
+        rmse (iters) f64, info int32[2] = (iterations made, reason: index into ICP_REASONS)), device tensors: gated point-to-point ICP
+        (yoho_icp_refine); entries of npairs / rmse behind the last iteration made hold -1."""
+        if src.dim() != 2 or tgt.dim() != 2 or src.shape[1] != 3 or tgt.shape[1] != 3 or T.numel() != 12:
+            raise ValueError("icp_refine: src (Ns,3), tgt (Nt,3), T (3,4)")
+        iters = int(iters)
+        T_out = torch.empty((3, 4), dtype=torch.float64, device=T.device)
+        npairs = torch.empty((max(iters, 0),), dtype=torch.int32, device=T.device)
+        rmse = torch.empty((max(iters, 0),), dtype=torch.float64, device=T.device)
+        info = torch.empty((2,), dtype=torch.int32, device=T.device)
+        _check(self._lib.yoho_icp_refine(self._h, _dev(src, torch.float32, "src"), src.shape[0], _dev(tgt, torch.float32, "tgt"), tgt.shape[0],
+                                         _dev(T, torch.float64, "T"), float(max_dist), iters, float(tol), C.c_void_p(T_out.data_ptr()),
+                                         C.c_void_p(npairs.data_ptr()) if iters > 0 else None, C.c_void_p(rmse.data_ptr()) if iters > 0 else None,
+                                         C.c_void_p(info.data_ptr()), _stream()))
+        return T_out, npairs, rmse, info
 
     def mutual_nn(self, a, b):
         """a (Na,32), b (Nb,32) -> (M,2) int64 mutual nearest neighbours, ascending in a."""

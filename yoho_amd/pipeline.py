@@ -15,7 +15,8 @@ import torch
 
 
 class PairResult:
-    __slots__ = ("match", "dr_index", "quat", "trans_pre", "best_h", "best_count", "trans", "order", "eqv", "range_repeats", "hyp_rows", "matches")
+    __slots__ = ("match", "dr_index", "quat", "trans_pre", "best_h", "best_count", "trans", "order", "eqv", "range_repeats", "hyp_rows", "matches",
+                 "trans_refined", "refine")
 
 
 def describe_pair(ctx, feat0, feat1, check_range=True):
@@ -30,7 +31,7 @@ def describe_pair(ctx, feat0, feat1, check_range=True):
 
 
 def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, order_rng=None, eqv=None, estimator="yohoo", seed=0,
-             hypotheses="all"):
+             hypotheses="all", refine=None, refine_iters=4, clouds=None, max_dist=None, icp_iters=30):
     """feat0/feat1 (K,32,60) f32 cuda (FCGF group features), keys0/keys1 (K,3) f64 cuda.
     estimator 'yohoo' (tests/evaluator.py:112-117: PartII + one-shot vote over <= max_iter per-match hypotheses, order
     shuffled by order_rng) or 'yohoc' (tests/evaluator.py:41-47: max_iter Kabsch RANSAC iterations sampled on the device
@@ -40,8 +41,25 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
     Match/Trans_pre (tests/extractor.py:142-201) - quat / trans_pre have M rows; "selected" = only for the min(max_iter, M) matches
     the vote will actually read (tests/estimator.py:321-326: T = Trans[index[:max_iter]]) - quat / trans_pre then have H rows in
     vote order, hyp_rows holds their match rows; winner, count and trans are identical (a match's PartII output does not depend on
-    which other matches share its pass), the other M - H hypotheses - which nothing downstream of the vote reads - are not computed."""
+    which other matches share its pass), the other M - H hypotheses - which nothing downstream of the vote reads - are not computed.
+    refine: None (default) = the estimator's transform is the result, nothing else runs; "refit" = the winner refitted on its inlier
+    matches (refine.refine_pair, refine_iters iterations); "refit+icp" = then polished by icp_iters iterations of gated ICP of
+    clouds = (cloud0, cloud1), (N,3) f32 cuda, inside max_dist.  Every field above stays what it is without refinement; trans_refined
+    (3,4) and refine (refine_pair's dict) are added - None when no hypothesis has an inlier."""
+    if refine not in (None, "refit", "refit+icp"):
+        raise ValueError(f"refine must be None, 'refit' or 'refit+icp', got {refine!r}")
+    if refine == "refit+icp" and (clouds is None or max_dist is None):
+        raise ValueError("refine='refit+icp' needs clouds=(cloud0, cloud1) and max_dist")
     r = PairResult()
+    r.trans_refined = r.refine = None
+
+    def refined(T_dev):
+        # the winner's transform is still on the device: it chains into the refit without another host read in front
+        from .refine import refine_pair
+        r.refine = refine_pair(ctx, keys0, keys1, r.match, T_dev, inlier_dist, iters=refine_iters, clouds=clouds if refine == "refit+icp" else None,
+                               max_dist=max_dist, icp_iters=icp_iters)
+        r.trans_refined = r.refine["trans"]
+
     r.range_repeats = 0
     r.quat = r.trans_pre = r.order = r.hyp_rows = None
     r.matches = 0
@@ -74,6 +92,8 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
         host = torch.cat([T.reshape(-1), res.to(torch.float64)]).cpu().numpy()
         r.best_h, r.best_count = int(host[12]), int(host[13])
         r.trans = host[:12].reshape(3, 4) if r.best_count > 0 else np.eye(4)
+        if refine is not None and r.best_count > 0:
+            refined(T)
         return r
     if estimator != "yohoo":
         raise ValueError(f"estimator must be 'yohoo' or 'yohoc', got {estimator!r}")
@@ -117,6 +137,8 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
         bh, bc = (int(v) for v in ctx._repeat_wider("partII", head_and_vote))
     r.best_h, r.best_count = bh, bc
     r.trans = r.trans_pre[bh if selected else int(order[bh])].cpu().numpy() if bc > 0 else np.eye(4)
+    if refine is not None and bc > 0:
+        refined(r.trans_pre[bh if selected else int(order[bh])])
     return r
 
 
@@ -179,7 +201,7 @@ class PairStreamer:
             r.range_repeats += 1
             return r
         r = PairResult()
-        r.match = r.dr_index = r.quat = r.trans_pre = r.order = r.hyp_rows = None
+        r.match = r.dr_index = r.quat = r.trans_pre = r.order = r.hyp_rows = r.trans_refined = r.refine = None
         r.eqv = (o0, o1)
         r.range_repeats = 0
         r.matches, r.best_h, r.best_count, r.trans = f["matches"], f["best_h"], f["best_count"], f["trans"]
