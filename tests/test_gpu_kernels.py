@@ -467,6 +467,23 @@ def test_partII_ragged_match_counts(ctx, ctxh, sd2, tables, M):
     assert ctxh.range_fallbacks == 0 and ctxh.range_repeats["partII"] == 0, ctxh.range_report()      # no pass repeated in bf16x3
 
 
+def test_partII_first_layer_blockings_are_bit_identical(hip, sd2, monkeypatch):
+    """YOHO_PARTII_L1=3 (read in yoho_ctx_create) runs PartII's first layer on fgemm3 instead of fgemm2: the two kernels share their K loop
+    and epilogue, so the quaternions have the same bits and neither context leaves the fp16 range - at the smallest match counts with one
+    ragged 32-match tile, a ragged 16-match tile, and a second, nearly empty 256-column tile"""
+    c2 = hip.Context()
+    monkeypatch.setenv("YOHO_PARTII_L1", "3")
+    c3 = hip.Context()
+    for c in (c2, c3):
+        c.load_partII(sd2)
+    for M in (1, 40, 257):
+        rs = np.random.RandomState(700 + M)
+        args = [cu(synth.unit_features(M, seed=sd)) for sd in (1, 2, 3, 4)] + [cu(rs.randint(0, 60, size=M).astype(np.int64))]
+        q2, q3 = c2.partII_forward(*args), c3.partII_forward(*args)
+        assert tuple(q2.shape) == (M, 4) and torch.equal(q2, q3), M
+    assert c2.range_fallbacks == 0 and c3.range_fallbacks == 0, (c2.range_report(), c3.range_report())
+
+
 @pytest.mark.parametrize("mode,tol", [("cgemm", TOL), ("cgemm8", TOL)])
 def test_partII_cone_gemm_modes(hip, ctx, ctxh, sd1, sd2, tables, mode, tol):
     """PartII modes 3 / 4: the 13-element cone layer as one implicit GEMM (cgemm_kernel: B-operand stage blocks picked per tap from the 45

@@ -372,7 +372,7 @@ int yoho_ctx_create(int device, const float* R, const uint8_t* N, const uint8_t*
         c->env.fcgf_norm_staged = is("YOHO_FCGF_NORM", "staged");
         c->env.fcgf_heads_staged = is("YOHO_FCGF_HEADS", "staged");
         if (const char* e = std::getenv("YOHO_WS_LIMIT_MB")) c->env.ws_limit_mb = std::atoll(e);
-        if (is("YOHO_PARTII_L1", "3")) c->env.partII_l1_variant = 3;
+        if (is("YOHO_PARTII_L1", "3")) c->env.partII_l1_variant = FG_TILE256_W8;
     }
     if (const char* m = std::getenv("YOHO_FCGF_CELLS")) c->fcgf_cell_sort = std::atoi(m);
     if (const char* m = std::getenv("YOHO_FCGF_SORT")) c->fcgf_parity_sort = std::strcmp(m, "0") == 0 ? 0 : 1;
@@ -775,7 +775,7 @@ static int partI_passG_chunk(yoho_ctx* c, char* ws, size_t slice, int evbase, co
                              const float* x1, int B0, int slot) {
     // GEMM blocking: mode 4 = 256 x 256 tile, eight waves (two per SIMD) sharing the A stage | mode 5 = 256 x 256, four waves (one per SIMD) |
     // mode 6 = 256 x 128 tiles, two four-wave workgroups per CU.  The transform kernel follows: two waves per SIMD except in mode 5.
-    const int gv = c->gconv_mode == 5 ? 1 : (c->gconv_mode == 6 ? 2 : 3);
+    const FGemmBlocking gv = c->gconv_mode == 5 ? FG_TILE256_W4 : (c->gconv_mode == 6 ? FG_TILE128 : FG_TILE256_W8);
     const int nT = (B + TILE - 1) / TILE;
     const int kppad = (B + 255) / 256 * 256;
     int rc;

@@ -90,6 +90,11 @@ struct Layer {
     float* bn_t = nullptr;    // [cout_pad] shift
 };
 
+// blockings of the irrep GEMMs (gemmf.hip / gemmf2.hip): one 256 x 256 tile per workgroup of four waves | 256 x 128 tiles, two four-wave
+// workgroups per CU | one 256 x 256 tile per workgroup of eight waves.  launch_gft16 takes the same choice: its transform runs two waves
+// per SIMD except beside FG_TILE256_W4.
+enum FGemmBlocking { FG_TILE256_W4 = 1, FG_TILE128 = 2, FG_TILE256_W8 = 3 };
+
 // epilogue flags
 enum { EPI_RES = 1, EPI_RAW = 2, EPI_ACT = 4, EPI_RAW32 = 8, EPI_ACT32 = 16 };
 
@@ -145,7 +150,7 @@ int launch_cgemm(const Layer& L, const char* Bstages, int nslot, const unsigned 
 int launch_gft16_invg(const float* in, float* res0, char* planesG, const int* slot_of, int nslot, const void* Ffrag, const float* bn_s,
                       const float* bn_t, int nTiles, int C8, int nCU, hipStream_t s, int* rflag, unsigned* amax);
 int launch_fgemm(const Layer& L, const char* Bplanes, int kppad, int nT32, const float* res, float* out, int flags, hipStream_t s,
-                 int* rflag = nullptr, int variant = 2, const unsigned* amax = nullptr);
+                 int* rflag = nullptr, FGemmBlocking blocking = FG_TILE128, const unsigned* amax = nullptr);
 void build_gft16_frags(const FourierBasis& fb, std::vector<unsigned short>& out);
 int gconv_layer(yoho_ctx* c, const float* x, int B, int cin, int cout, const float* W, const float* bias, int transpose, float* y,
                 hipStream_t s);
@@ -276,7 +281,7 @@ struct yoho_env_switches {
     bool fcgf_full_maps = false;       // YOHO_FCGF_MAPS=full: every kernel map by its own probes (no mirrored / inverted maps)
     bool fcgf_norm_staged = false;     // YOHO_FCGF_NORM=staged: row normalisation as its own kernel behind the last convolution
     bool fcgf_heads_staged = false;    // YOHO_FCGF_HEADS=staged: the decoder's two 1 x 1 heads as two launches (heads_fused_kernel off); identical bits
-    int partII_l1_variant = 2;         // YOHO_PARTII_L1=3: PartII's first (Fourier) layer on fgemm3 (256 x 256 tiles, eight waves) instead of fgemm2
+    yoho::FGemmBlocking partII_l1_variant = yoho::FG_TILE128;   // YOHO_PARTII_L1=3: PartII's first (Fourier) layer on fgemm3 (FG_TILE256_W8) instead of fgemm2
     long long ws_limit_mb = 0;         // YOHO_WS_LIMIT_MB=<n>: a workspace request above n MiB fails as an exhausted device would (0 = no limit):
                                        // lets a test walk the YOHO_ENOMEM recoveries of the backbone (hash-table attempt, table voxelisation)
 };

@@ -98,23 +98,9 @@ __global__ __launch_bounds__(256, 1) void fgemm_kernel(FGemmArgs a, int flags) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // Work map.  Workgroup b runs on XCD b & 7.  A column tile (irrep t, ntile) and its MT[t] row tiles stay on one XCD
-    // (the B panel is then read from HBM once and served from that XCD's L2 to the other row tiles); the column tiles
-    // of every irrep are dealt round-robin over the XCDs so that all eight get the same mix of long and short K loops.
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    int t = -1, local = 0, r = 0;
-    {
-        int start = 0;
-#pragma unroll
-        for (int u = 0; u < NIR_ORD; ++u) {
-            const int ru = (xcd + a.rot[u]) & 7;
-            const int cnt = a.NT[u] > ru ? ((a.NT[u] - 1 - ru) / 8 + 1) * a.MT[u] : 0;
-            if (t < 0 && slot < start + cnt) { t = u; local = slot - start; r = ru; }
-            start += cnt;
-        }
-    }
-    if (t < 0) return;
-    const int d = a.dim[t], qbase = a.qbase[t];
+    int t = 0, local = 0, r = 0;
+    if (!fg3_map(a, blockIdx.x & 7, blockIdx.x >> 3, t, local, r)) return;
+    const int d = a.dim[t];
     const int MT = a.MT[t], KS = d * a.cin / 32;
     const int cg = local / MT, mtile = local - cg * MT;
     const int ntile = r + 8 * cg;
@@ -122,14 +108,12 @@ __global__ __launch_bounds__(256, 1) void fgemm_kernel(FGemmArgs a, int flags) {
     const char* Bg = a.B + a.b_off[t] + (size_t)ntile * KS * FG_STAGE;
     const int wm = w >> 1, wn = w & 1;
     const int lane16 = lane * 16;
+    const int row0 = mtile * 256 + wm * 128;
+    const int col0 = ntile * 256 + wn * 128;            // kp0 = col0 % kppad and jidx = col0 / kppad are worked out where they are used, not
+                                                        // carried through the K loop: this kernel has no register to spare
 
     floatx16 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // LDS: buffer u at u * 64 KiB: A tile, then B tile
     const int lane_a = (lane >> 5) * 4096 + (wm * 128 + (lane & 31)) * 16;
@@ -141,39 +125,11 @@ __global__ __launch_bounds__(256, 1) void fgemm_kernel(FGemmArgs a, int flags) {
         stage_tile(Ag + FG_STAGE, smem + 2 * FG_STAGE, w, lane);
         stage_tile(Bg + FG_STAGE, smem + 3 * FG_STAGE, w, lane);
     }
-    if ((flags & EPI_RES) && (mtile * 256 + wm * 128) < d * a.cout) {
-        // The accumulators start from the residual (scaled by 1 / descale, a power of two): its 64 loads per wave are in
-        // flight together with the first two DMA stages.  Added in the epilogue instead they are serialised behind the
-        // accumulators' registers (no room to prefetch) and cost a third of a millisecond per pass.
-        const float inv = 1.f / a.descale;
-        const int half = lane >> 5, kp32 = lane & 31, cout8 = a.cout >> 3;
-        const int col0 = ntile * 256 + wn * 128;
-        const int jidx = col0 / a.kppad, kp0 = col0 - jidx * a.kppad;
-#pragma unroll
-        for (int bi = 0; bi < 4; ++bi) {
-            const int tile32 = (kp0 >> 5) + bi;
-#pragma unroll
-            for (int ai = 0; ai < 4; ++ai) {
-                const int rowb = mtile * 256 + wm * 128 + ai * 32;
-                const int iidx = rowb / a.cout, o0 = rowb - iidx * a.cout;
-                const bool ok = tile32 < a.nT32 && iidx < d;
-                const int q = qbase + iidx * d + jidx;
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const int o = o0 + q4 * 8 + half * 4;
-                    const size_t off = (((((size_t)tile32 * G + q) * cout8 + (o >> 3)) * 2 + half) * TILE + kp32) * 4;
-                    // branch-free, so that all loads go out back to back
-                    const floatx4 v = *reinterpret_cast<const floatx4*>(a.res + (ok ? off : 0)) * (ok ? inv : 0.f);
-                    acc[ai][bi][4 * q4 + 0] = v.x; acc[ai][bi][4 * q4 + 1] = v.y;
-                    acc[ai][bi][4 * q4 + 2] = v.z; acc[ai][bi][4 * q4 + 3] = v.w;
-                }
-            }
-        }
-    }
+    if ((flags & EPI_RES) && row0 < d * a.cout) residual_start(acc, row0, col0 % a.kppad, col0 / a.kppad, d, a.qbase[t], a.res, a.descale, a.cout, a.nT32, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
-    if ((mtile * 256 + wm * 128) >= d * a.cout) {
+    if (row0 >= d * a.cout) {
         // all 128 rows of this wave are padding (small cout): only keep the LDS DMA and the barriers going
         for (int s = 0; s < KS; ++s) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -205,41 +161,7 @@ __global__ __launch_bounds__(256, 1) void fgemm_kernel(FGemmArgs a, int flags) {
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-    // ---- epilogue: D[row][col]: lane (col = lane & 31, half = lane >> 5), reg r -> row = (r & 3) + 8 * (r >> 2) + 4 * half
-    const int half = lane >> 5, kp32 = lane & 31;
-    const int cout8 = a.cout >> 3;
-    const int col0 = ntile * 256 + wn * 128;
-    const int jidx = col0 / a.kppad, kp0 = col0 - jidx * a.kppad;
-    const bool addb = (d == 1);                              // trivial irrep: coefficient 0 carries sqrt(60) * bias
-    unsigned top = 0u;                                       // largest |coefficient| written (bit pattern; inf / NaN order above)
-#pragma unroll
-    for (int bi = 0; bi < 4; ++bi) {
-        const int tile32 = (kp0 >> 5) + bi;
-        if (tile32 >= a.nT32) continue;
-#pragma unroll
-        for (int ai = 0; ai < 4; ++ai) {
-            // the 32 rows of an MFMA tile share i (cout is a multiple of 32)
-            const int rowb = mtile * 256 + wm * 128 + ai * 32;
-            const int iidx = rowb / a.cout, o0 = rowb - iidx * a.cout;
-            if (iidx >= d) continue;
-            const int q = qbase + iidx * d + jidx;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int o = o0 + q4 * 8 + half * 4;
-                floatx4 val;
-                val.x = acc[ai][bi][4 * q4 + 0]; val.y = acc[ai][bi][4 * q4 + 1];
-                val.z = acc[ai][bi][4 * q4 + 2]; val.w = acc[ai][bi][4 * q4 + 3];
-                val *= a.descale;
-                if (addb) val += *reinterpret_cast<const floatx4*>(a.bias + o) * 7.745966692414834f;
-                const size_t off = (((((size_t)tile32 * G + q) * cout8 + (o >> 3)) * 2 + half) * TILE + kp32) * 4;
-                *reinterpret_cast<floatx4*>(a.out + off) = val;
-                top = max(max(top, __float_as_uint(val.x) & 0x7FFFFFFFu), __float_as_uint(val.y) & 0x7FFFFFFFu);
-                top = max(max(top, __float_as_uint(val.z) & 0x7FFFFFFFu), __float_as_uint(val.w) & 0x7FFFFFFFu);
-            }
-        }
-    }
-    // the transform kernel that reads these coefficients multiplies them by HF_ASCALE and converts to fp16
-    note_range_bits(a.rflag, top, FP16_MAX / HF_ASCALE);
+    coef_epilogue(acc, row0, col0 % a.kppad, col0 / a.kppad, d, a.qbase[t], a.out, a.bias, a.descale, a.cout, a.nT32, a.rflag, lane, flags);
 }
 
 int fgemm_init() {
@@ -304,9 +226,35 @@ static inline float half_value_h(unsigned short u) {
     return (float)h;
 }
 
-// What(r,i,m)[o][c] = sum_k W[o][c][k] rho_r(n_k)[m][i]  ->  A pack (fp16x2 planes of What * 2^s)
-// out8 (optional): the pack fgemm3c reads - the hi plane as in `out`; every 16-byte unit of the lo plane (the 8 K-values of one row and
+// element index of (row, k) inside an A pack whose 256-row tiles hold KS stages: [tile][stage K32][plane 2][sub-step 2][k-group 2][row 256][8]
+static inline size_t apack_index(int row, int k, int KS) {
+    const int mtile = row >> 8, rr = row & 255, ks = k >> 5, sub = (k >> 4) & 1, kg = (k >> 3) & 1, e = k & 7;
+    return ((size_t)mtile * KS + ks) * (FG_STAGE / 2) + ((size_t)(sub * 2 + kg) * 256 + rr) * 8 + e;
+}
+// x = hi + lo into the two fp16 planes of its stage (8192 halfs apart)
+static inline void put_split(unsigned short* pack, size_t idx, float x) {
+    const _Float16 hi = (_Float16)x;
+    pack[idx] = half_bits_h(x);
+    pack[idx + 8192] = half_bits_h(x - (float)hi);
+}
+// out8 = the pack fgemm3c / cgemm<true> read: the hi plane as in `out`; every 16-byte unit of the lo plane (the 8 K-values of one row and
 // k-group) replaced by the unit's fp8 operand: bytes 0-7 = e4m3(hi / 4), bytes 8-15 = e4m3(lo * 512)   (|hi| < 1024, |lo| <= 0.5)
+static void fp8_correction_planes(const std::vector<unsigned short>& out, std::vector<unsigned short>& out8) {
+    out8 = out;
+    const size_t nblk = out.size() / (FG_STAGE / 2);
+    for (size_t b = 0; b < nblk; ++b) {
+        const unsigned short* src = out.data() + b * (FG_STAGE / 2);
+        unsigned char* dst = reinterpret_cast<unsigned char*>(out8.data() + b * (FG_STAGE / 2) + 8192);
+        for (int u = 0; u < 1024; ++u)                                     // 16-byte units of the plane
+            for (int e = 0; e < 8; ++e) {
+                dst[u * 16 + e] = e4m3_bits(half_value_h(src[u * 8 + e]) * 0.25f);
+                dst[u * 16 + 8 + e] = e4m3_bits(half_value_h(src[8192 + u * 8 + e]) * 512.f);
+            }
+    }
+}
+
+// What(r,i,m)[o][c] = sum_k W[o][c][k] rho_r(n_k)[m][i]  ->  A pack (fp16x2 planes of What * 2^s)
+// out8 (optional): the pack fgemm3c reads (fp8_correction_planes)
 int pack_fgemm_weights(const FourierBasis& fb, const float* W, int cin, int cout, std::vector<unsigned short>& out, float* descale,
                        std::vector<unsigned short>* out8) {
     if ((cout % 256 && cout != 32) || cin % 32) return -1;     // row tiles must not straddle i unless the whole irrep fits one tile
@@ -336,38 +284,15 @@ int pack_fgemm_weights(const FourierBasis& fb, const float* W, int cin, int cout
     out.assign((size_t)pack_off(NIR_ORD, cout, cin) / 2, 0);
     for (int t = 0; t < NIR_ORD; ++t) {
         const int r = FG_ORD_R[t], d = FG_IR_D[r];
-        const int KS = d * cin / 32;
         unsigned short* base = out.data() + pack_off(t, cout, cin) / 2;
         for (int i = 0; i < d; ++i)
-            for (int o = 0; o < cout; ++o) {
-                const int row = i * cout + o, mtile = row >> 8, rr = row & 255;
+            for (int o = 0; o < cout; ++o)
                 for (int m = 0; m < d; ++m) {
                     const float* src = &what[((size_t)(FG_IR_BASE[r] + i * d + m) * cout + o) * cin];
-                    for (int c = 0; c < cin; ++c) {
-                        const int k = m * cin + c, ks = k >> 5, sub = (k >> 4) & 1, kg = (k >> 3) & 1, e = k & 7;
-                        const float x = src[c] * wscale;
-                        const _Float16 hi = (_Float16)x;
-                        unsigned short* blk = base + ((size_t)mtile * KS + ks) * (FG_STAGE / 2);
-                        const size_t idx = ((size_t)(sub * 2 + kg) * 256 + rr) * 8 + e;      // within a plane (8192 halfs per plane-substep pair)
-                        blk[0 * 8192 + idx] = half_bits_h(x);
-                        blk[1 * 8192 + idx] = half_bits_h(x - (float)hi);
-                    }
+                    for (int c = 0; c < cin; ++c) put_split(base, apack_index(i * cout + o, m * cin + c, d * cin / 32), src[c] * wscale);
                 }
-            }
     }
-    if (out8) {
-        *out8 = out;
-        const size_t nblk = out.size() / (FG_STAGE / 2);
-        for (size_t b = 0; b < nblk; ++b) {
-            const unsigned short* src = out.data() + b * (FG_STAGE / 2);
-            unsigned char* dst = reinterpret_cast<unsigned char*>(out8->data() + b * (FG_STAGE / 2) + 8192);
-            for (int u = 0; u < 1024; ++u)                                     // 16-byte units of the plane
-                for (int e = 0; e < 8; ++e) {
-                    dst[u * 16 + e] = e4m3_bits(half_value_h(src[u * 8 + e]) * 0.25f);
-                    dst[u * 16 + 8 + e] = e4m3_bits(half_value_h(src[8192 + u * 8 + e]) * 512.f);
-                }
-        }
-    }
+    if (out8) fp8_correction_planes(out, *out8);
     return 0;
 }
 
@@ -383,30 +308,10 @@ int pack_cgemm_weights(const float* W, int cin, int cout, int ntaps, std::vector
     *descale = 1.f / (wscale * H2_ASCALE);
     const int KS = ntaps * cin / 32;
     out.assign((size_t)(cout / 256) * KS * (FG_STAGE / 2), 0);
-    for (int o = 0; o < cout; ++o) {
-        const int mtile = o >> 8, rr = o & 255;
+    for (int o = 0; o < cout; ++o)
         for (int tap = 0; tap < ntaps; ++tap)
-            for (int c = 0; c < cin; ++c) {
-                const int k = tap * cin + c, ks = k >> 5, sub = (k >> 4) & 1, kg = (k >> 3) & 1, e = k & 7;
-                const float x = W[((size_t)o * cin + c) * ntaps + tap] * wscale;
-                const _Float16 hi = (_Float16)x;
-                unsigned short* blk = out.data() + ((size_t)mtile * KS + ks) * (FG_STAGE / 2);
-                const size_t idx = ((size_t)(sub * 2 + kg) * 256 + rr) * 8 + e;
-                blk[0 * 8192 + idx] = half_bits_h(x);
-                blk[1 * 8192 + idx] = half_bits_h(x - (float)hi);
-            }
-    }
-    out8 = out;
-    const size_t nblk = out.size() / (FG_STAGE / 2);
-    for (size_t b = 0; b < nblk; ++b) {
-        const unsigned short* src = out.data() + b * (FG_STAGE / 2);
-        unsigned char* dst = reinterpret_cast<unsigned char*>(out8.data() + b * (FG_STAGE / 2) + 8192);
-        for (int u = 0; u < 1024; ++u)
-            for (int e = 0; e < 8; ++e) {
-                dst[u * 16 + e] = e4m3_bits(half_value_h(src[u * 8 + e]) * 0.25f);
-                dst[u * 16 + 8 + e] = e4m3_bits(half_value_h(src[8192 + u * 8 + e]) * 512.f);
-            }
-    }
+            for (int c = 0; c < cin; ++c) put_split(out.data(), apack_index(o, tap * cin + c, KS), W[((size_t)o * cin + c) * ntaps + tap] * wscale);
+    fp8_correction_planes(out, out8);
     return 0;
 }
 
@@ -426,28 +331,19 @@ void fgemm_fill_args(FGemmArgs& a, const Layer& L, const char* Bplanes, int kppa
     }
 }
 
-// variant 2 (default): 256 x 128 tiles, two workgroups per CU (gemmf2.hip); variant 1: 256 x 256 tiles, one workgroup per CU
+// the blockings of the irrep GEMMs: one 256 x 256 tile in four waves (gemmf.hip) | 256 x 128 tiles, two four-wave workgroups per CU
+// (fgemm2: PartII's first layer) | one 256 x 256 tile in eight waves sharing the A stage (fgemm3 / fgemm3s / fgemm3c: PartI's default)
 int launch_fgemm(const Layer& L, const char* Bplanes, int kppad, int nT32, const float* res, float* out, int flags, hipStream_t s, int* rflag,
-                 int variant, const unsigned* amax) {
+                 FGemmBlocking blocking, const unsigned* amax) {
     FGemmArgs a;
     fgemm_fill_args(a, L, Bplanes, kppad, nT32, res, out, rflag);
     static const int dbg_gemm1 = [] { const char* e = experiment_env("YOHO_PARTI_DEBUG"); return (e && std::strstr(e, "gemm1")) ? 1 : 0; }();
-    if (dbg_gemm1) variant = 1;
-    // fgemm3c and its fp8 weight pack - chosen AFTER every override of the variant: the other kernels read A as fp16 planes
-    if (variant == 3 && amax && L.wpg8) { a.amax = amax; a.A = reinterpret_cast<const char*>(L.wpg8); }
-    if (variant == 3) return launch_fgemm3(a, flags, s);
-    if (variant != 1) return launch_fgemm2(a, flags, s);
-    int tot = 0;
-    for (int x = 0; x < 8; ++x) {
-        int n = 0;
-        for (int t = 0; t < NIR_ORD; ++t) {
-            const int r = (x + a.rot[t]) & 7;
-            if (a.NT[t] > r) n += ((a.NT[t] - 1 - r) / 8 + 1) * a.MT[t];
-        }
-        tot = n > tot ? n : tot;
-    }
-    tot *= 8;
-    hipLaunchKernelGGL(fgemm_kernel, dim3(tot), dim3(256), FG_LDS, s, a, flags);
+    if (dbg_gemm1) blocking = FG_TILE256_W4;
+    // fgemm3c and its fp8 weight pack - chosen AFTER every override of the blocking: the other kernels read A as fp16 planes
+    if (blocking == FG_TILE256_W8 && amax && L.wpg8) { a.amax = amax; a.A = reinterpret_cast<const char*>(L.wpg8); }
+    if (blocking == FG_TILE256_W8) return launch_fgemm3(a, flags, s);
+    if (blocking != FG_TILE256_W4) return launch_fgemm2(a, flags, s);
+    hipLaunchKernelGGL(fgemm_kernel, dim3(fgemm_grid(a, 1)), dim3(256), FG_LDS, s, a, flags);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -22,61 +22,85 @@
 
 namespace yoho {
 
-constexpr int F2_BUF = 24576;                 // one ring buffer: A 16 KiB [plane 2][k-group 2][row 256][16 B] | B 8 KiB [plane 2][k-group 2][col 128][16 B]
+constexpr int F2_BUF = 24576;                 // fgemm2's ring buffer: A 16 KiB [plane 2][k-group 2][row 256][16 B] | B 8 KiB [plane 2][k-group 2][col 128][16 B]
 constexpr int F2_LDS = 3 * F2_BUF;
+constexpr int F3_BUF = 32768;                 // fgemm3's: the same A | B 16 KiB [plane 2][k-group 2][col 256][16 B]
+constexpr int F3_LDS = 3 * F3_BUF;
 
 struct Frags2 {
     uintx4 ah[4], al[4], bh[2], bl[2];
 };
 
-// fragment read R (0..11) of a step, in the order of use: A lo x4, B hi x2 (products lo.hi), A hi x4, B lo x2
-template <int R>
+// fragment read R (0..11) of a step, in the order of use: A lo x4, B hi x2 (products lo.hi), A hi x4, B lo x2; LO = offset of B's lo plane
+template <int LO, int R>
 __device__ __forceinline__ void read_frag2(const char* pa, const char* pb, Frags2& f) {
     if constexpr (R < 4) f.al[R] = *reinterpret_cast<const uintx4*>(pa + 8192 + R * 512);
     else if constexpr (R < 6) f.bh[R - 4] = *reinterpret_cast<const uintx4*>(pb + (R - 4) * 512);
     else if constexpr (R < 10) f.ah[R - 6] = *reinterpret_cast<const uintx4*>(pa + (R - 6) * 512);
-    else f.bl[R - 10] = *reinterpret_cast<const uintx4*>(pb + 4096 + (R - 10) * 512);
+    else f.bl[R - 10] = *reinterpret_cast<const uintx4*>(pb + LO + (R - 10) * 512);
+}
+template <int LO>
+__device__ __forceinline__ void read_frags2(const char* pa, const char* pb, Frags2& f) {
+    sfor<0, 12>([&](auto rc) { read_frag2<LO, decltype(rc)::value>(pa, pb, f); });
 }
 
-// piece U (0..5) of this wave's share of the DMA of one K16 step: 1 KiB each.  srcA / srcB point at the step inside the packs
-// (stage * 32 KiB + sub-step * 8 KiB, wave uniform), la / lb are the per-lane byte offsets inside the A and B parts.
-template <int U>
-__device__ __forceinline__ void dma_piece(const char* srcA, const char* srcB, char* buf, int la, int lb, int w, int wkg, int wcb) {
-    if constexpr (U < 4) {
-        constexpr int plane = U >> 1, kg = U & 1;                       // A: piece (plane, kg, 64-row block w)
-        __builtin_amdgcn_global_load_lds((gptr_t)(srcA + plane * 16384 + kg * 4096 + la), (lptr_t)(buf + plane * 8192 + kg * 4096 + w * 1024), 16, 0, 0);
-    } else {
-        constexpr int plane = U - 4;                                    // B: piece (plane, kg = w >> 1, 64-column block w & 1)
-        __builtin_amdgcn_global_load_lds((gptr_t)(srcB + plane * 16384 + lb), (lptr_t)(buf + 16384 + plane * 4096 + wkg * 2048 + wcb * 1024), 16, 0, 0);
+// A wave's share of the LDS DMA of one K16 step, in pieces of 1 KiB.  srcA / srcB point at the step inside the packs (stage * 32 KiB +
+// sub-step * 8 KiB, wave uniform).  fgemm2 (four waves, 24 KiB): six pieces; la / lb are the per-lane byte offsets inside the A and B parts.
+struct Dma2 {
+    static constexpr int NP = 6, LO = 4096;
+    int la, lb, w;
+    __device__ __forceinline__ Dma2(int w_, int lane) : la(w_ * 1024 + lane * 16), lb((w_ >> 1) * 4096 + (w_ & 1) * 1024 + lane * 16), w(w_) {}
+    template <int U>
+    __device__ __forceinline__ void piece(const char* srcA, const char* srcB, char* buf) const {
+        if constexpr (U < 4) {
+            constexpr int plane = U >> 1, kg = U & 1;                       // A: piece (plane, kg, 64-row block w)
+            __builtin_amdgcn_global_load_lds((gptr_t)(srcA + plane * 16384 + kg * 4096 + la), (lptr_t)(buf + plane * 8192 + kg * 4096 + w * 1024), 16, 0, 0);
+        } else {
+            constexpr int plane = U - 4;                                    // B: piece (plane, kg = w >> 1, 64-column block w & 1)
+            __builtin_amdgcn_global_load_lds((gptr_t)(srcB + plane * 16384 + lb), (lptr_t)(buf + 16384 + plane * 4096 + (w >> 1) * 2048 + (w & 1) * 1024), 16, 0, 0);
+        }
     }
+};
+// the 256 x 256 tiles (eight waves, 32 KiB): four pieces, U = 0, 1: A plane U; U = 2, 3: B plane U - 2; the wave's (k-group w8 >> 2, 64-row /
+// 64-column block w8 & 3) is folded into `la` (source, the same for the A and the B piece) and `ldst` (destination)
+struct Dma3 {
+    static constexpr int NP = 4, LO = 8192;
+    int la, ldst;
+    __device__ __forceinline__ Dma3(int w8, int lane) : la(w8 * 1024 + lane * 16), ldst(w8 * 1024) {}
+    template <int U>
+    __device__ __forceinline__ void piece(const char* srcA, const char* srcB, char* buf) const {
+        constexpr int plane = U & 1;
+        if constexpr (U < 2) __builtin_amdgcn_global_load_lds((gptr_t)(srcA + plane * 16384 + la), (lptr_t)(buf + plane * 8192 + ldst), 16, 0, 0);
+        else __builtin_amdgcn_global_load_lds((gptr_t)(srcB + plane * 16384 + la), (lptr_t)(buf + 16384 + plane * 8192 + ldst), 16, 0, 0);
+    }
+};
+template <typename Dma>
+__device__ __forceinline__ void dma_step(const Dma& dm, const char* srcA, const char* srcB, char* buf) {
+    sfor<0, Dma::NP>([&](auto uc) { dm.template piece<decltype(uc)::value>(srcA, srcB, buf); });
 }
 
-__device__ __forceinline__ void dma_step(const char* srcA, const char* srcB, char* buf, int la, int lb, int w, int wkg, int wcb) {
-    sfor<0, 6>([&](auto uc) { dma_piece<decltype(uc)::value>(srcA, srcB, buf, la, lb, w, wkg, wcb); });
-}
-
-// One K16 step: 24 MFMAs on `f` (every accumulator gets lo.hi, hi.lo, hi.hi, 8 MFMAs apart); behind them, one per MFMA, the
-// 12 fragment reads of the next step and (DMA) the six DMA pieces of the step three ahead.
-template <bool DMA>
-__device__ __forceinline__ void step2(const Frags2& f, floatx16 (&acc)[4][2], const char* ra, const char* rb, Frags2& nf,
-                                      const char* srcA, const char* srcB, char* dmabuf, int la, int lb, int w, int wkg, int wcb) {
+// One K16 step: 24 MFMAs on `f` (every accumulator gets lo.hi, hi.lo, hi.hi, 8 MFMAs apart); behind them, one per MFMA, the 12 fragment
+// reads of the next step and (DMA) the wave's DMA pieces of the step three ahead: piece p rides behind MFMA 12 + p.
+template <bool DMA, typename Dma>
+__device__ __forceinline__ void step2(const Dma& dm, const Frags2& f, floatx16 (&acc)[4][2], const char* ra, const char* rb, Frags2& nf,
+                                      const char* srcA, const char* srcB, char* dmabuf) {
     sfor<0, 8>([&](auto gc) {
         constexpr int g = decltype(gc)::value;
         acc[g >> 1][g & 1] = mfma_h(f.al[g >> 1], f.bh[g & 1], acc[g >> 1][g & 1]);
-        read_frag2<g>(ra, rb, nf);
+        read_frag2<Dma::LO, g>(ra, rb, nf);
         __builtin_amdgcn_sched_barrier(0);
     });
     sfor<0, 8>([&](auto gc) {
         constexpr int g = decltype(gc)::value;
         acc[g >> 1][g & 1] = mfma_h(f.ah[g >> 1], f.bl[g & 1], acc[g >> 1][g & 1]);
-        if constexpr (g < 4) read_frag2<8 + g>(ra, rb, nf);
-        else if constexpr (DMA && g >= 4 && g < 8) dma_piece<g - 4>(srcA, srcB, dmabuf, la, lb, w, wkg, wcb);
+        if constexpr (g < 4) read_frag2<Dma::LO, 8 + g>(ra, rb, nf);
+        else if constexpr (DMA) dm.template piece<g - 4>(srcA, srcB, dmabuf);
         __builtin_amdgcn_sched_barrier(0);
     });
     sfor<0, 8>([&](auto gc) {
         constexpr int g = decltype(gc)::value;
         acc[g >> 1][g & 1] = mfma_h(f.ah[g >> 1], f.bh[g & 1], acc[g >> 1][g & 1]);
-        if constexpr (DMA && g < 2) dma_piece<4 + g>(srcA, srcB, dmabuf, la, lb, w, wkg, wcb);
+        if constexpr (DMA && 4 + g < Dma::NP) dm.template piece<4 + g>(srcA, srcB, dmabuf);
         __builtin_amdgcn_sched_barrier(0);
     });
 }
@@ -87,7 +111,6 @@ __device__ __forceinline__ void step2(const Frags2& f, floatx16 (&acc)[4][2], co
 // tile - so the slots of an XCD alternate between the d = 5 irrep (long K loops: 40000 of an XCD's 78000 steps for 256 -> 512)
 // and the other four (shorter K loops, in launch order): co-resident workgroups then have different lengths and drift apart
 // after the first round.  Returns false for a slot beyond the XCD's work.
-enum { F2_NOSTORE = 0x100, F2_MIX = 0x200, F2_ST_SC1 = 0x400, F2_ST_NT = 0x800, F2_SPARSE4 = 0x1000, F2_SPARSE16 = 0x2000 };   // YOHO_FGEMM_DEBUG experiments, see launch_fgemm2
 __host__ __device__ inline bool fg2_map(const FGemmArgs& a, int xcd, int slot, bool contiguous, int& t, int& local, int& r) {
     int cnt[NIR_ORD], ru[NIR_ORD];
     for (int u = 0; u < NIR_ORD; ++u) {
@@ -117,6 +140,75 @@ __host__ __device__ inline bool fg2_map(const FGemmArgs& a, int xcd, int slot, b
 // byte offset of K16 step ks inside a tile's pack: stage (ks >> 1) * 32 KiB + sub-step (ks & 1) * 8 KiB
 __device__ __forceinline__ size_t step_off(int ks) { return (size_t)(ks >> 1) * FG_STAGE + (size_t)(ks & 1) * 8192; }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The pipelined ring (fgemm2, fgemm3, fgemm3s).  Step s lives in buffer s % 3 of BUF bytes.  In iteration s a wave issues its MFMAs on
+// the fragments of step s (registers), reads the fragments of step s + 1 from the ring and issues its INFLIGHT pieces of the DMA of
+// step s + 3 into the buffer of step s; `s_waitcnt vmcnt(INFLIGHT)` (the pieces just issued stay in flight) and one barrier then make
+// step s + 2 readable.  P: the fragments of step 0, read by the caller behind the prologue's barrier; step(dma, f, nf, ra, rb, srcA, srcB,
+// dmabuf) is the kernel's step function (dma: std::bool_constant).
+// ---------------------------------------------------------------------------------------------------------------
+template <int BUF, typename Dma>
+__device__ __forceinline__ void ring_prologue(int KT, Dma&& dma) {      // steps 0, 1, 2 into the three buffers
+    dma(0, 0);
+    dma(1, BUF);
+    if (KT > 2) dma(2, 2 * BUF);
+}
+
+template <int BUF, int INFLIGHT, typename F, typename Step>
+__device__ __forceinline__ void ring_pipelined(char* smem, const char* Ag, const char* Bg, int KT, int lane_a, int lane_b, F& P, Step&& step) {
+    F Q;
+    // Every wave must have step 0 in registers before ANY wave overwrites buffer 0 with step 3 (the first DMA of the loop below):
+    // inside the loop the barrier at the end of step s - 1 orders the reads of step s before the DMA of step s + 3, but between
+    // the prologue's barrier and the first step there was nothing - a wave delayed by a few hundred cycles (cold instruction
+    // cache at the head of a launch) read step 3's rows in place of step 0's.  Found in round 3 by the depth-first schedule
+    // (many short launches), whose outputs differed from the breadth-first pass in whole 32-keypoint wave tiles.
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    int cur = 0, nxt = BUF;                      // buffer of step s (already in registers: the target of the DMA of step s + 3), of step s + 1
+    int s = 0;
+    // step s on f, the fragments of step s + 1 into nf
+    auto run = [&](auto dma, const F& f, F& nf) {
+        if constexpr (decltype(dma)::value) {
+            step(dma, f, nf, smem + nxt + lane_a, smem + nxt + lane_b, uniform_ptr(Ag + step_off(s + 3)), uniform_ptr(Bg + step_off(s + 3)), smem + cur);
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(INFLIGHT) : "memory");
+        } else {
+            step(dma, f, nf, smem + nxt + lane_a, smem + nxt + lane_b, nullptr, nullptr, nullptr);
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        cur = nxt; nxt = nxt == 2 * BUF ? 0 : nxt + BUF; ++s;
+    };
+    constexpr std::true_type dma;
+    constexpr std::false_type nodma;
+    // main loop: both steps of a pair still have a DMA to issue
+    while (s + 4 < KT) {
+        run(dma, P, Q);
+        run(dma, Q, P);
+    }
+    // tail: the last four steps (two if KT == 2); only the first of them still has a DMA (step KT - 1) to issue
+    if (KT >= 4) {
+        run(dma, P, Q);
+        run(nodma, Q, P);
+    }
+    run(nodma, P, Q);
+    // last step: its "next" fragments are read from a buffer that holds valid (unused) data
+    step(nodma, Q, P, smem + cur + lane_a, smem + cur + lane_b, nullptr, nullptr, nullptr);
+}
+
+// a wave whose 128 rows are all padding (cout = 32): keep its share of the DMA and the barriers going (the live waves meet at one
+// barrier per step but the last)
+template <int BUF, typename Dma>
+__device__ __forceinline__ void ring_pipelined_idle(int KT, Dma&& dma) {
+    __builtin_amdgcn_s_barrier();                              // the live waves' barrier behind their reads of step 0
+    for (int s = 0; s + 1 < KT; ++s) {
+        if (s + 3 < KT) dma(s + 3, (s % 3) * BUF);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    }
+}
+
 __global__ __launch_bounds__(256, 2) void fgemm2_kernel(FGemmArgs a, int flags) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -125,7 +217,7 @@ __global__ __launch_bounds__(256, 2) void fgemm2_kernel(FGemmArgs a, int flags) 
     // same A stages at about the same time, so one of the two reads hits the XCD's L2
     int t = 0, local = 0, r = 0;
     if (!fg2_map(a, blockIdx.x & 7, blockIdx.x >> 3, (flags & F2_MIX) == 0, t, local, r)) return;
-    const int d = a.dim[t], qbase = a.qbase[t];
+    const int d = a.dim[t];
     const int MT = a.MT[t], KS = d * a.cin / 32, KT = 2 * KS;
     const int nh = local & 1, pair = local >> 1;
     const int cg = pair / MT, mtile = pair - cg * MT;
@@ -133,149 +225,29 @@ __global__ __launch_bounds__(256, 2) void fgemm2_kernel(FGemmArgs a, int flags) 
     const char* Ag = a.A + a.a_off[t] + (size_t)mtile * KS * FG_STAGE;
     const char* Bg = a.B + a.b_off[t] + (size_t)ntile * KS * FG_STAGE + nh * 2048;
     const int wm = w >> 1, wn = w & 1;
-    const int wkg = w >> 1, wcb = w & 1;                                 // this wave's B piece: k-group, 64-column block
-    const int la = w * 1024 + lane * 16;                                 // DMA source offsets inside a step
-    const int lb = wkg * 4096 + wcb * 1024 + lane * 16;
-
-    floatx16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
+    const Dma2 dm(w, lane);
     const int lane_a = (lane >> 5) * 4096 + (wm * 128 + (lane & 31)) * 16;
     const int lane_b = 16384 + (lane >> 5) * 2048 + (wn * 64 + (lane & 31)) * 16;
 
-    // prologue: steps 0, 1, 2 into the three buffers
-    dma_step(Ag, Bg, smem, la, lb, w, wkg, wcb);
-    dma_step(Ag + step_off(1), Bg + step_off(1), smem + F2_BUF, la, lb, w, wkg, wcb);
-    if (KT > 2) dma_step(Ag + step_off(2), Bg + step_off(2), smem + 2 * F2_BUF, la, lb, w, wkg, wcb);
-    const bool rows_live = (mtile * 256 + wm * 128) < d * a.cout;       // else: all 128 rows of this wave are padding (cout = 32)
-    const int colbase = ntile * 256 + nh * 128 + wn * 64;
-    const int jidx = colbase / a.kppad, kp0 = colbase - jidx * a.kppad;
-    if ((flags & EPI_RES) && rows_live) {
-        // the accumulators start from the residual (x 1 / descale, a power of two): its loads fly with the first DMA stages
-        const float inv = 1.f / a.descale;
-        const int half = lane >> 5, kp32 = lane & 31, cout8 = a.cout >> 3;
-#pragma unroll
-        for (int bi = 0; bi < 2; ++bi) {
-            const int tile32 = (kp0 >> 5) + bi;
-#pragma unroll
-            for (int ai = 0; ai < 4; ++ai) {
-                const int rowb = mtile * 256 + wm * 128 + ai * 32;
-                const int iidx = rowb / a.cout, o0 = rowb - iidx * a.cout;
-                const bool ok = tile32 < a.nT32 && iidx < d;
-                const int q = qbase + iidx * d + jidx;
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const int o = o0 + q4 * 8 + half * 4;
-                    const size_t off = (((((size_t)tile32 * G + q) * cout8 + (o >> 3)) * 2 + half) * TILE + kp32) * 4;
-                    const floatx4 v = *reinterpret_cast<const floatx4*>(a.res + (ok ? off : 0)) * (ok ? inv : 0.f);     // branch-free
-                    acc[ai][bi][4 * q4 + 0] = v.x; acc[ai][bi][4 * q4 + 1] = v.y;
-                    acc[ai][bi][4 * q4 + 2] = v.z; acc[ai][bi][4 * q4 + 3] = v.w;
-                }
-            }
-        }
-    }
+    floatx16 acc[4][2];
+    zero_acc(acc);
+    auto dma = [&](int st, int buf) { dma_step(dm, Ag + step_off(st), Bg + step_off(st), smem + buf); };
+    ring_prologue<F2_BUF>(KT, dma);
+    const int row0 = mtile * 256 + wm * 128, colbase = ntile * 256 + nh * 128 + wn * 64;
+    const bool rows_live = row0 < d * a.cout;       // else: all 128 rows of this wave are padding (cout = 32)
+    const int jidx = colbase / a.kppad, kp0 = colbase - jidx * a.kppad, qbase = a.qbase[t];
+    if ((flags & EPI_RES) && rows_live) residual_start(acc, row0, kp0, jidx, d, qbase, a.res, a.descale, a.cout, a.nT32, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+    if (!rows_live) return ring_pipelined_idle<F2_BUF>(KT, dma);
 
-    if (!rows_live) {
-        // keep this wave's share of the DMA and the barriers going (the live waves meet at one barrier per step but the last)
-        __builtin_amdgcn_s_barrier();                          // the live waves' barrier behind their reads of step 0 (below)
-        for (int s = 0; s + 1 < KT; ++s) {
-            if (s + 3 < KT) dma_step(Ag + step_off(s + 3), Bg + step_off(s + 3), smem + (s % 3) * F2_BUF, la, lb, w, wkg, wcb);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-        return;
-    }
-
-    Frags2 P, Q;
-    sfor<0, 12>([&](auto rc) { read_frag2<decltype(rc)::value>(smem + lane_a, smem + lane_b, P); });
-    // every wave has step 0 in registers before any wave's first DMA (step 3) lands in buffer 0 (see fgemm3s_kloop)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ring offsets: step s lives in buffer s % 3
-    int cur = 0, nxt = F2_BUF;                   // buffer of step s (already in registers: the target of the DMA of step s+3), of step s+1
-    int s = 0;
-    auto advance = [&]() { cur = nxt; nxt = nxt == 2 * F2_BUF ? 0 : nxt + F2_BUF; ++s; };
-    // main loop: both steps of a pair still have a DMA to issue (s + 4 < KT)
-    for (; s + 4 < KT;) {
-        step2<true>(P, acc, smem + nxt + lane_a, smem + nxt + lane_b, Q, uniform_ptr(Ag + step_off(s + 3)), uniform_ptr(Bg + step_off(s + 3)),
-                    smem + cur, la, lb, w, wkg, wcb);
-        asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        advance();
-        step2<true>(Q, acc, smem + nxt + lane_a, smem + nxt + lane_b, P, uniform_ptr(Ag + step_off(s + 3)), uniform_ptr(Bg + step_off(s + 3)),
-                    smem + cur, la, lb, w, wkg, wcb);
-        asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        advance();
-    }
-    // tail: the last four steps (two if KT == 2); only the first of them still has a DMA (step KT - 1) to issue
-    if (KT >= 4) {
-        step2<true>(P, acc, smem + nxt + lane_a, smem + nxt + lane_b, Q, uniform_ptr(Ag + step_off(s + 3)), uniform_ptr(Bg + step_off(s + 3)),
-                    smem + cur, la, lb, w, wkg, wcb);
-        asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        advance();
-        step2<false>(Q, acc, smem + nxt + lane_a, smem + nxt + lane_b, P, nullptr, nullptr, nullptr, la, lb, w, wkg, wcb);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        advance();
-    }
-    step2<false>(P, acc, smem + nxt + lane_a, smem + nxt + lane_b, Q, nullptr, nullptr, nullptr, la, lb, w, wkg, wcb);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    advance();
-    // last step: its "next" fragments are read from a buffer that holds valid (unused) data
-    step2<false>(Q, acc, smem + cur + lane_a, smem + cur + lane_b, P, nullptr, nullptr, nullptr, la, lb, w, wkg, wcb);
-
-    // ---- epilogue: D[row][col]: lane (col = lane & 31, half = lane >> 5), reg e -> row = (e & 3) + 8 * (e >> 2) + 4 * half
-    const int half = lane >> 5, kp32 = lane & 31;
-    const int cout8 = a.cout >> 3;
-    const bool addb = (d == 1);                              // trivial irrep: coefficient 0 carries sqrt(60) * bias
-    if ((flags & F2_SPARSE4) && (blockIdx.x >> 3) % 4 != 0) flags |= F2_NOSTORE;          // experiment: only every 4th / 16th workgroup stores
-    if ((flags & F2_SPARSE16) && (blockIdx.x >> 3) % 16 != 0) flags |= F2_NOSTORE;
-    unsigned top = 0u;                                       // largest |coefficient| written (bit pattern; inf / NaN order above)
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, 0x7FFFFFFF, 0x00020000);
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi) {
-        const int tile32 = (kp0 >> 5) + bi;
-        if (tile32 >= a.nT32) continue;
-#pragma unroll
-        for (int ai = 0; ai < 4; ++ai) {
-            const int rowb = mtile * 256 + wm * 128 + ai * 32;     // the 32 rows of an MFMA tile share i (cout is a multiple of 32)
-            const int iidx = rowb / a.cout, o0 = rowb - iidx * a.cout;
-            if (iidx >= d) continue;
-            const int q = qbase + iidx * d + jidx;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int o = o0 + q4 * 8 + half * 4;
-                floatx4 val;
-                val.x = acc[ai][bi][4 * q4 + 0]; val.y = acc[ai][bi][4 * q4 + 1];
-                val.z = acc[ai][bi][4 * q4 + 2]; val.w = acc[ai][bi][4 * q4 + 3];
-                val *= a.descale;
-                if (addb) val += *reinterpret_cast<const floatx4*>(a.bias + o) * 7.745966692414834f;
-                const size_t off = (((((size_t)tile32 * G + q) * cout8 + (o >> 3)) * 2 + half) * TILE + kp32) * 4;
-                if (flags & F2_ST_SC1) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, val), orsrc, (int)(off * 4), 0, 16);
-                else if (flags & F2_ST_NT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, val), orsrc, (int)(off * 4), 0, 2);
-                else if (!(flags & F2_NOSTORE)) *reinterpret_cast<floatx4*>(a.out + off) = val;
-                top = max(max(top, __float_as_uint(val.x) & 0x7FFFFFFFu), __float_as_uint(val.y) & 0x7FFFFFFFu);
-                top = max(max(top, __float_as_uint(val.z) & 0x7FFFFFFFu), __float_as_uint(val.w) & 0x7FFFFFFFu);
-            }
-        }
-    }
-    note_range_bits(a.rflag, top, FP16_MAX / HF_ASCALE);     // the consumer multiplies by HF_ASCALE and converts to fp16
+    Frags2 P;
+    read_frags2<Dma2::LO>(smem + lane_a, smem + lane_b, P);
+    ring_pipelined<F2_BUF, 6>(smem, Ag, Bg, KT, lane_a, lane_b, P,
+        [&](auto dmac, const Frags2& f, Frags2& nf, const char* ra, const char* rb, const char* srcA, const char* srcB, char* buf) {
+            step2<decltype(dmac)::value>(dm, f, acc, ra, rb, nf, srcA, srcB, buf);
+        });
+    coef_epilogue(acc, row0, kp0, jidx, d, qbase, a.out, a.bias, a.descale, a.cout, a.nT32, a.rflag, lane, flags);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -283,225 +255,49 @@ __global__ __launch_bounds__(256, 2) void fgemm2_kernel(FGemmArgs a, int flags) 
 // The halves share the A stage in LDS, so the L2 -> LDS traffic and the fabric traffic are those of the 256 x 256 blocking
 // (a step is 16 KiB of A + 16 KiB of B, ring of three 32 KiB buffers = 96 KiB), while every SIMD still has two waves.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int F3_BUF = 32768;                 // A 16 KiB [plane 2][k-group 2][row 256][16 B] | B 16 KiB [plane 2][k-group 2][col 256][16 B]
-constexpr int F3_LDS = 3 * F3_BUF;
-
-template <int R>
-__device__ __forceinline__ void read_frag3(const char* pa, const char* pb, Frags2& f) {
-    if constexpr (R < 4) f.al[R] = *reinterpret_cast<const uintx4*>(pa + 8192 + R * 512);
-    else if constexpr (R < 6) f.bh[R - 4] = *reinterpret_cast<const uintx4*>(pb + (R - 4) * 512);
-    else if constexpr (R < 10) f.ah[R - 6] = *reinterpret_cast<const uintx4*>(pa + (R - 6) * 512);
-    else f.bl[R - 10] = *reinterpret_cast<const uintx4*>(pb + 8192 + (R - 10) * 512);
-}
-
-// piece U (0..3) of a wave's share of a step's DMA (32 pieces of 1 KiB over 8 waves): U = 0, 1: A plane U; U = 2, 3: B plane U - 2;
-// the wave's (k-group, 64-row/column block) is folded into `la` (source) and `ldst` (destination)
-template <int U>
-__device__ __forceinline__ void dma_piece3(const char* srcA, const char* srcB, char* buf, int la, int ldst) {
-    constexpr int plane = U & 1;
-    if constexpr (U < 2) __builtin_amdgcn_global_load_lds((gptr_t)(srcA + plane * 16384 + la), (lptr_t)(buf + plane * 8192 + ldst), 16, 0, 0);
-    else __builtin_amdgcn_global_load_lds((gptr_t)(srcB + plane * 16384 + la), (lptr_t)(buf + 16384 + plane * 8192 + ldst), 16, 0, 0);
-}
-
-__device__ __forceinline__ void dma_step3(const char* srcA, const char* srcB, char* buf, int la, int lb, int w, int wkg, int wcb) {
-    const int ldst = wkg * 4096 + wcb * 1024;
-    sfor<0, 4>([&](auto uc) { dma_piece3<decltype(uc)::value>(srcA, srcB, buf, la, ldst); });
-}
-
-template <bool DMA>
-__device__ __forceinline__ void step3(const Frags2& f, floatx16 (&acc)[4][2], const char* ra, const char* rb, Frags2& nf,
-                                      const char* srcA, const char* srcB, char* dmabuf, int la, int lb, int w, int wkg, int wcb) {
-    const int ldst = wkg * 4096 + wcb * 1024;
-    sfor<0, 8>([&](auto gc) {
-        constexpr int g = decltype(gc)::value;
-        acc[g >> 1][g & 1] = mfma_h(f.al[g >> 1], f.bh[g & 1], acc[g >> 1][g & 1]);
-        read_frag3<g>(ra, rb, nf);
-        __builtin_amdgcn_sched_barrier(0);
-    });
-    sfor<0, 8>([&](auto gc) {
-        constexpr int g = decltype(gc)::value;
-        acc[g >> 1][g & 1] = mfma_h(f.ah[g >> 1], f.bl[g & 1], acc[g >> 1][g & 1]);
-        if constexpr (g < 4) read_frag3<8 + g>(ra, rb, nf);
-        else if constexpr (DMA) dma_piece3<g - 4>(srcA, srcB, dmabuf, la, ldst);
-        __builtin_amdgcn_sched_barrier(0);
-    });
-    sfor<0, 8>([&](auto gc) {
-        constexpr int g = decltype(gc)::value;
-        acc[g >> 1][g & 1] = mfma_h(f.ah[g >> 1], f.bh[g & 1], acc[g >> 1][g & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-    });
-}
-
-// work map of gemmf.hip (one workgroup per 256 x 256 tile)
-__host__ __device__ inline bool fg3_map(const FGemmArgs& a, int xcd, int slot, int& t, int& local, int& r) {
-    int start = 0;
-    for (int u = 0; u < NIR_ORD; ++u) {
-        const int ru = (xcd + a.rot[u]) & 7;
-        const int cnt = a.NT[u] > ru ? ((a.NT[u] - 1 - ru) / 8 + 1) * a.MT[u] : 0;
-        if (slot < start + cnt) { t = u; local = slot - start; r = ru; return true; }
-        start += cnt;
+// What fgemm3, fgemm3c and cgemm share: waves 0-3 own the left 128 columns of the tile, 4-7 the right; in a half, 2 (rows) x 2 (columns) waves
+struct Wave3 {
+    int wm, wn, nh, lane_a, lane_b;
+    Dma3 dm;
+    __device__ __forceinline__ Wave3(int w8, int lane) : wm((w8 & 3) >> 1), wn(w8 & 1), nh(w8 >> 2), dm(w8, lane) {
+        lane_a = (lane >> 5) * 4096 + (wm * 128 + (lane & 31)) * 16;
+        lane_b = 16384 + (lane >> 5) * 4096 + (nh * 128 + wn * 64 + (lane & 31)) * 16;
     }
-    return false;
-}
+};
 
 __global__ __launch_bounds__(512, 2) void fgemm3_kernel(FGemmArgs a, int flags) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);             // 8 waves: waves 0-3 own the left 128 columns, 4-7 the right
-    const int w = w8 & 3;
+    const Wave3 wv(__builtin_amdgcn_readfirstlane(tid >> 6), lane);
     int t = 0, local = 0, r = 0;
     if (!fg3_map(a, blockIdx.x & 7, blockIdx.x >> 3, t, local, r)) return;
-    const int d = a.dim[t], qbase = a.qbase[t];
+    const int d = a.dim[t];
     const int MT = a.MT[t], KS = d * a.cin / 32, KT = 2 * KS;
-    const int nh = w8 >> 2, pair = local;
-    const int cg = pair / MT, mtile = pair - cg * MT;
+    const int cg = local / MT, mtile = local - cg * MT;
     const int ntile = r + 8 * cg;
     const char* Ag = a.A + a.a_off[t] + (size_t)mtile * KS * FG_STAGE;
     const char* Bg = a.B + a.b_off[t] + (size_t)ntile * KS * FG_STAGE;
-    const int wm = w >> 1, wn = w & 1;
-    const int wkg = w8 >> 2, wcb = w8 & 3;                               // this wave's DMA pieces: k-group, 64-row / 64-column block
-    const int la = wkg * 4096 + wcb * 1024 + lane * 16;                  // DMA source offset inside a step (same for the A and the B piece)
-    const int lb = la;
 
     floatx16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    const int lane_a = (lane >> 5) * 4096 + (wm * 128 + (lane & 31)) * 16;
-    const int lane_b = 16384 + (lane >> 5) * 4096 + (nh * 128 + wn * 64 + (lane & 31)) * 16;
-
-    // prologue: steps 0, 1, 2 into the three buffers
-    dma_step3(Ag, Bg, smem, la, lb, w, wkg, wcb);
-    dma_step3(Ag + step_off(1), Bg + step_off(1), smem + F3_BUF, la, lb, w, wkg, wcb);
-    if (KT > 2) dma_step3(Ag + step_off(2), Bg + step_off(2), smem + 2 * F3_BUF, la, lb, w, wkg, wcb);
-    const bool rows_live = (mtile * 256 + wm * 128) < d * a.cout;       // else: all 128 rows of this wave are padding (cout = 32)
-    const int colbase = ntile * 256 + nh * 128 + wn * 64;
-    const int jidx = colbase / a.kppad, kp0 = colbase - jidx * a.kppad;
-    if ((flags & EPI_RES) && rows_live) {
-        // the accumulators start from the residual (x 1 / descale, a power of two): its loads fly with the first DMA stages
-        const float inv = 1.f / a.descale;
-        const int half = lane >> 5, kp32 = lane & 31, cout8 = a.cout >> 3;
-#pragma unroll
-        for (int bi = 0; bi < 2; ++bi) {
-            const int tile32 = (kp0 >> 5) + bi;
-#pragma unroll
-            for (int ai = 0; ai < 4; ++ai) {
-                const int rowb = mtile * 256 + wm * 128 + ai * 32;
-                const int iidx = rowb / a.cout, o0 = rowb - iidx * a.cout;
-                const bool ok = tile32 < a.nT32 && iidx < d;
-                const int q = qbase + iidx * d + jidx;
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const int o = o0 + q4 * 8 + half * 4;
-                    const size_t off = (((((size_t)tile32 * G + q) * cout8 + (o >> 3)) * 2 + half) * TILE + kp32) * 4;
-                    const floatx4 v = *reinterpret_cast<const floatx4*>(a.res + (ok ? off : 0)) * (ok ? inv : 0.f);     // branch-free
-                    acc[ai][bi][4 * q4 + 0] = v.x; acc[ai][bi][4 * q4 + 1] = v.y;
-                    acc[ai][bi][4 * q4 + 2] = v.z; acc[ai][bi][4 * q4 + 3] = v.w;
-                }
-            }
-        }
-    }
+    zero_acc(acc);
+    auto dma = [&](int st, int buf) { dma_step(wv.dm, Ag + step_off(st), Bg + step_off(st), smem + buf); };
+    ring_prologue<F3_BUF>(KT, dma);
+    const int row0 = mtile * 256 + wv.wm * 128, colbase = ntile * 256 + wv.nh * 128 + wv.wn * 64;
+    const bool rows_live = row0 < d * a.cout;       // else: all 128 rows of this wave are padding (cout = 32)
+    const int jidx = colbase / a.kppad, kp0 = colbase - jidx * a.kppad, qbase = a.qbase[t];
+    if ((flags & EPI_RES) && rows_live) residual_start(acc, row0, kp0, jidx, d, qbase, a.res, a.descale, a.cout, a.nT32, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
+    if (!rows_live) return ring_pipelined_idle<F3_BUF>(KT, dma);
 
-    if (!rows_live) {
-        // keep this wave's share of the DMA and the barriers going (the live waves meet at one barrier per step but the last)
-        __builtin_amdgcn_s_barrier();                          // the live waves' barrier behind their reads of step 0 (below)
-        for (int s = 0; s + 1 < KT; ++s) {
-            if (s + 3 < KT) dma_step3(Ag + step_off(s + 3), Bg + step_off(s + 3), smem + (s % 3) * F3_BUF, la, lb, w, wkg, wcb);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
-        return;
-    }
-
-    Frags2 P, Q;
-    sfor<0, 12>([&](auto rc) { read_frag3<decltype(rc)::value>(smem + lane_a, smem + lane_b, P); });
-    // every wave has step 0 in registers before any wave's first DMA (step 3) lands in buffer 0 (see fgemm3s_kloop)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ring offsets: step s lives in buffer s % 3
-    int cur = 0, nxt = F3_BUF;                   // buffer of step s (already in registers: the target of the DMA of step s+3), of step s+1
-    int s = 0;
-    auto advance = [&]() { cur = nxt; nxt = nxt == 2 * F3_BUF ? 0 : nxt + F3_BUF; ++s; };
-    // main loop: both steps of a pair still have a DMA to issue (s + 4 < KT)
-    for (; s + 4 < KT;) {
-        step3<true>(P, acc, smem + nxt + lane_a, smem + nxt + lane_b, Q, uniform_ptr(Ag + step_off(s + 3)), uniform_ptr(Bg + step_off(s + 3)),
-                    smem + cur, la, lb, w, wkg, wcb);
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        advance();
-        step3<true>(Q, acc, smem + nxt + lane_a, smem + nxt + lane_b, P, uniform_ptr(Ag + step_off(s + 3)), uniform_ptr(Bg + step_off(s + 3)),
-                    smem + cur, la, lb, w, wkg, wcb);
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        advance();
-    }
-    // tail: the last four steps (two if KT == 2); only the first of them still has a DMA (step KT - 1) to issue
-    if (KT >= 4) {
-        step3<true>(P, acc, smem + nxt + lane_a, smem + nxt + lane_b, Q, uniform_ptr(Ag + step_off(s + 3)), uniform_ptr(Bg + step_off(s + 3)),
-                    smem + cur, la, lb, w, wkg, wcb);
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        advance();
-        step3<false>(Q, acc, smem + nxt + lane_a, smem + nxt + lane_b, P, nullptr, nullptr, nullptr, la, lb, w, wkg, wcb);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        advance();
-    }
-    step3<false>(P, acc, smem + nxt + lane_a, smem + nxt + lane_b, Q, nullptr, nullptr, nullptr, la, lb, w, wkg, wcb);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    advance();
-    // last step: its "next" fragments are read from a buffer that holds valid (unused) data
-    step3<false>(Q, acc, smem + cur + lane_a, smem + cur + lane_b, P, nullptr, nullptr, nullptr, la, lb, w, wkg, wcb);
-
-    // ---- epilogue: D[row][col]: lane (col = lane & 31, half = lane >> 5), reg e -> row = (e & 3) + 8 * (e >> 2) + 4 * half
-    const int half = lane >> 5, kp32 = lane & 31;
-    const int cout8 = a.cout >> 3;
-    const bool addb = (d == 1);                              // trivial irrep: coefficient 0 carries sqrt(60) * bias
-        unsigned top = 0u;                                       // largest |coefficient| written (bit pattern; inf / NaN order above)
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, 0x7FFFFFFF, 0x00020000);
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi) {
-        const int tile32 = (kp0 >> 5) + bi;
-        if (tile32 >= a.nT32) continue;
-#pragma unroll
-        for (int ai = 0; ai < 4; ++ai) {
-            const int rowb = mtile * 256 + wm * 128 + ai * 32;     // the 32 rows of an MFMA tile share i (cout is a multiple of 32)
-            const int iidx = rowb / a.cout, o0 = rowb - iidx * a.cout;
-            if (iidx >= d) continue;
-            const int q = qbase + iidx * d + jidx;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int o = o0 + q4 * 8 + half * 4;
-                floatx4 val;
-                val.x = acc[ai][bi][4 * q4 + 0]; val.y = acc[ai][bi][4 * q4 + 1];
-                val.z = acc[ai][bi][4 * q4 + 2]; val.w = acc[ai][bi][4 * q4 + 3];
-                val *= a.descale;
-                if (addb) val += *reinterpret_cast<const floatx4*>(a.bias + o) * 7.745966692414834f;
-                const size_t off = (((((size_t)tile32 * G + q) * cout8 + (o >> 3)) * 2 + half) * TILE + kp32) * 4;
-                if (flags & F2_ST_SC1) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, val), orsrc, (int)(off * 4), 0, 16);
-                else if (flags & F2_ST_NT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, val), orsrc, (int)(off * 4), 0, 2);
-                else if (!(flags & F2_NOSTORE)) *reinterpret_cast<floatx4*>(a.out + off) = val;
-                top = max(max(top, __float_as_uint(val.x) & 0x7FFFFFFFu), __float_as_uint(val.y) & 0x7FFFFFFFu);
-                top = max(max(top, __float_as_uint(val.z) & 0x7FFFFFFFu), __float_as_uint(val.w) & 0x7FFFFFFFu);
-            }
-        }
-    }
-    note_range_bits(a.rflag, top, FP16_MAX / HF_ASCALE);     // the consumer multiplies by HF_ASCALE and converts to fp16
+    Frags2 P;
+    read_frags2<Dma3::LO>(smem + wv.lane_a, smem + wv.lane_b, P);
+    ring_pipelined<F3_BUF, 4>(smem, Ag, Bg, KT, wv.lane_a, wv.lane_b, P,
+        [&](auto dmac, const Frags2& f, Frags2& nf, const char* ra, const char* rb, const char* srcA, const char* srcB, char* buf) {
+            step2<decltype(dmac)::value>(wv.dm, f, acc, ra, rb, nf, srcA, srcB, buf);
+        });
+    coef_epilogue(acc, row0, kp0, jidx, d, qbase, a.out, a.bias, a.descale, a.cout, a.nT32, a.rflag, lane, flags);
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------
 // fgemm3c (gconv_mode 7, "fgemm8"; round 5, opt-in): fgemm3 with the two CORRECTION products of the fp16 split on the fp8 matrix pipe.
@@ -522,9 +318,22 @@ typedef _Float16 halfx2 __attribute__((ext_vector_type(2)));
 struct Frags8 {
     intx8 a[4], b[2];          // dwords [4 p .. 4 p + 1] = hi plane (A) / lo plane (B) of the pair's step p, [4 p + 2 .. 4 p + 3] = lo (A) / hi (B)
 };
+// fp8 conversion scales (the conversion DIVIDES by its scale operand; powers of two throughout).  Weights: max |What| * wscale is in
+// [2^9, 2^10) (pack_fgemm_weights) -> / 4 puts the hi plane below 256 (e4m3 tops out at 448); their lo plane is 2^-11 of that.
+// Activations: the producer of the planes left the largest magnitude it wrote in *amax (bit pattern of a non-negative float):
+// 2^k with k = floor(log2(amax)) - 7 puts it into [128, 256).  Both correction products then carry 1 / (4 * 2^k * 2^-11), undone by
+// the block scales of the MFMA (E8M0, 127 = 2^0).
 struct C8Scales {
-    float ah, al, bh, bl;
-    int mfma_b;
+    float ah = 4.f, al = 4.f / 2048.f, bh = 1.f, bl = 1.f;
+    int mfma_b = 127;
+    C8Scales() = default;
+    __device__ __forceinline__ explicit C8Scales(const unsigned* amax) {
+        const unsigned amax_bits = __builtin_amdgcn_readfirstlane(*amax);
+        int kexp = (int)(amax_bits >> 23) - 127 - 7;
+        kexp = kexp < -60 ? -60 : (kexp > 9 ? 9 : kexp);
+        bh = __uint_as_float((unsigned)(kexp + 127) << 23); bl = __uint_as_float((unsigned)(kexp - 11 + 127) << 23);
+        mfma_b = 127 + kexp;
+    }
 };
 struct Int2 { int x, y; };
 // eight fp16 (one fragment) / scale -> eight fp8 e4m3 (two dwords)
@@ -570,115 +379,59 @@ __device__ __forceinline__ void step3c(const Frags2& f, floatx16 (&acc)[4][2], F
     }
 }
 
-__global__ __launch_bounds__(512, 2) void fgemm3c_kernel(FGemmArgs a, int flags) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);             // 8 waves: waves 0-3 own the left 128 columns, 4-7 the right
-    const int w = w8 & 3;
-    int t = 0, local = 0, r = 0;
-    if (!fg3_map(a, blockIdx.x & 7, blockIdx.x >> 3, t, local, r)) return;
-    const int d = a.dim[t], qbase = a.qbase[t];
-    const int MT = a.MT[t], KS = d * a.cin / 32, KT = 2 * KS;
-    const int nh = w8 >> 2, pair = local;
-    const int cg = pair / MT, mtile = pair - cg * MT;
-    const int ntile = r + 8 * cg;
-    const char* Ag = a.A + a.a_off[t] + (size_t)mtile * KS * FG_STAGE;
-    const char* Bg = a.B + a.b_off[t] + (size_t)ntile * KS * FG_STAGE;
-    const int wm = w >> 1, wn = w & 1;
-    const int wkg = w8 >> 2, wcb = w8 & 3;                               // this wave's DMA pieces: k-group, 64-row / 64-column block
-    const int la = wkg * 4096 + wcb * 1024 + lane * 16;                  // DMA source offset inside a step (same for the A and the B piece)
-    const int lb = la;
-
-    floatx16 acc[4][2];
+// The plain ring (fgemm3c, cgemm) behind a prologue that staged steps 0 and 1.  Step s lives in ring buffer s % 3.  At the head of step
+// s: its DMA (issued two steps ago) has landed - the four pieces issued one step ago may stay in flight -, one barrier, then the DMA of
+// step s + 2 goes into the buffer every wave finished reading BEFORE that barrier (step s - 1's), the twelve fragments of step s are read,
+// and the products are issued: the two waves of a SIMD cover each other's fragment latency (tools/fp8_corr_probe.hip: this plain loop
+// runs the three-product arithmetic as fast as fgemm3's hand-interleaved one).  Past the end the last step is staged again (into a
+// buffer nobody reads any more): uniform counted waits.  bsrc(s) = B source of step s; FP8: corrections on the fp8 pipe (step3c).
+template <bool FP8, typename BSrc>
+__device__ __forceinline__ void ring_plain(floatx16 (&acc)[4][2], char* smem, const Wave3& wv, const char* Ag, BSrc&& bsrc, int KT, bool rows_live,
+                                           const C8Scales& sc) {
+    Frags8 c8;
+    if constexpr (FP8) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) c8.a[i][e] = 0;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    // fp8 conversion scales (the conversion DIVIDES by its scale operand; powers of two throughout).  Weights: max |What| * wscale is in
-    // [2^9, 2^10) (pack_fgemm_weights) -> / 4 puts the hi plane below 256 (e4m3 tops out at 448); their lo plane is 2^-11 of that.
-    // Activations: the producer of the planes left the largest magnitude it wrote in *a.amax (bit pattern of a non-negative float):
-    // 2^k with k = floor(log2(amax)) - 7 puts it into [128, 256).  Both correction products then carry 1 / (4 * 2^k * 2^-11), undone by
-    // the block scales of the MFMA (E8M0, 127 = 2^0).
-    const unsigned amax_bits = __builtin_amdgcn_readfirstlane(*a.amax);
-    int kexp = (int)(amax_bits >> 23) - 127 - 7;
-    kexp = kexp < -60 ? -60 : (kexp > 9 ? 9 : kexp);
-    C8Scales sc;
-    sc.ah = 4.f; sc.al = 4.f / 2048.f;
-    sc.bh = __uint_as_float((unsigned)(kexp + 127) << 23); sc.bl = __uint_as_float((unsigned)(kexp - 11 + 127) << 23);
-    sc.mfma_b = 127 + kexp;
-    const int lane_a = (lane >> 5) * 4096 + (wm * 128 + (lane & 31)) * 16;
-    const int lane_b = 16384 + (lane >> 5) * 4096 + (nh * 128 + wn * 64 + (lane & 31)) * 16;
-
-    // prologue: steps 0 and 1 (the loop stages two steps ahead of the one it multiplies)
-    dma_step3(Ag, Bg, smem, la, lb, w, wkg, wcb);
-    dma_step3(Ag + step_off(1), Bg + step_off(1), smem + F3_BUF, la, lb, w, wkg, wcb);
-    const bool rows_live = (mtile * 256 + wm * 128) < d * a.cout;       // else: all 128 rows of this wave are padding (cout = 32)
-    const int colbase = ntile * 256 + nh * 128 + wn * 64;
-    const int jidx = colbase / a.kppad, kp0 = colbase - jidx * a.kppad;
-    if ((flags & EPI_RES) && rows_live) {
-        // the accumulators start from the residual (x 1 / descale, a power of two): its loads fly with the first DMA stages
-        const float inv = 1.f / a.descale;
-        const int half = lane >> 5, kp32 = lane & 31, cout8 = a.cout >> 3;
-#pragma unroll
-        for (int bi = 0; bi < 2; ++bi) {
-            const int tile32 = (kp0 >> 5) + bi;
-#pragma unroll
-            for (int ai = 0; ai < 4; ++ai) {
-                const int rowb = mtile * 256 + wm * 128 + ai * 32;
-                const int iidx = rowb / a.cout, o0 = rowb - iidx * a.cout;
-                const bool ok = tile32 < a.nT32 && iidx < d;
-                const int q = qbase + iidx * d + jidx;
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const int o = o0 + q4 * 8 + half * 4;
-                    const size_t off = (((((size_t)tile32 * G + q) * cout8 + (o >> 3)) * 2 + half) * TILE + kp32) * 4;
-                    const floatx4 v = *reinterpret_cast<const floatx4*>(a.res + (ok ? off : 0)) * (ok ? inv : 0.f);     // branch-free
-                    acc[ai][bi][4 * q4 + 0] = v.x; acc[ai][bi][4 * q4 + 1] = v.y;
-                    acc[ai][bi][4 * q4 + 2] = v.z; acc[ai][bi][4 * q4 + 3] = v.w;
-                }
-            }
-        }
+            for (int e = 0; e < 8; ++e) c8.b[j][e] = 0;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-
-    Frags8 c8;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) c8.a[i][e] = 0;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) c8.b[j][e] = 0;
-    // Step s lives in ring buffer s % 3.  At the head of step s: its DMA (issued two steps ago) has landed - the four pieces issued one
-    // step ago may stay in flight -, one barrier, then the DMA of step s + 2 goes into the buffer every wave finished reading BEFORE that
-    // barrier (step s - 1's), the twelve fragments of step s are read, and the products are issued: the two waves of a SIMD cover each
-    // other's fragment latency (tools/fp8_corr_probe.hip: this plain loop runs the three-product arithmetic as fast as fgemm3's
-    // hand-interleaved one).  Past the end the last step is staged again (into a buffer nobody reads any more): uniform counted waits.
     int cur = 0, stg = 2 * F3_BUF;                // buffer of step s, buffer the DMA of step s + 2 goes to
     int s = 0;
+    auto stage = [&] {
+        const int s2 = s + 2 < KT ? s + 2 : KT - 1;
+        dma_step(wv.dm, uniform_ptr(Ag + step_off(s2)), uniform_ptr(bsrc(s2)), smem + stg);
+    };
+    auto rotate = [&] { stg = cur; cur = cur == 2 * F3_BUF ? 0 : cur + F3_BUF; ++s; };      // (s + 3) % 3 == s % 3
     auto one_step = [&](auto parity) {
-        constexpr int PAR = decltype(parity)::value;
         asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        {
-            const int s2 = s + 2 < KT ? s + 2 : KT - 1;
-            dma_step3(uniform_ptr(Ag + step_off(s2)), uniform_ptr(Bg + step_off(s2)), smem + stg, la, lb, w, wkg, wcb);
-        }
+        stage();
         Frags2 f;
-        sfor<0, 12>([&](auto rc) { read_frag3<decltype(rc)::value>(smem + cur + lane_a, smem + cur + lane_b, f); });
-        step3c<PAR>(f, acc, c8, sc);
-        stg = cur;                               // (s + 3) % 3 == s % 3
-        cur = cur == 2 * F3_BUF ? 0 : cur + F3_BUF;
-        ++s;
+        read_frags2<Dma3::LO>(smem + cur + wv.lane_a, smem + cur + wv.lane_b, f);
+        if constexpr (FP8) step3c<decltype(parity)::value>(f, acc, c8, sc);
+        else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = mfma_h(f.al[i], f.bh[j], acc[i][j]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = mfma_h(f.ah[i], f.bl[j], acc[i][j]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = mfma_h(f.ah[i], f.bh[j], acc[i][j]);
+        }
+        rotate();
     };
     if (rows_live) {
-        for (int it = 0; it < KT; it += 2) {     // KT = 2 KS is even
+        for (int it = 0; it < KT; it += 2) {     // KT is even
             one_step(std::integral_constant<int, 0>{});
             one_step(std::integral_constant<int, 1>{});
         }
@@ -687,53 +440,41 @@ __global__ __launch_bounds__(512, 2) void fgemm3c_kernel(FGemmArgs a, int flags)
         for (int it = 0; it < KT; ++it) {
             asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            const int s2 = s + 2 < KT ? s + 2 : KT - 1;
-            dma_step3(uniform_ptr(Ag + step_off(s2)), uniform_ptr(Bg + step_off(s2)), smem + stg, la, lb, w, wkg, wcb);
-            stg = cur;
-            cur = cur == 2 * F3_BUF ? 0 : cur + F3_BUF;
-            ++s;
+            stage();
+            rotate();
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the re-staged tail pieces must not land in the LDS of the next workgroup
-    if (!rows_live) return;
-
-    // ---- epilogue: D[row][col]: lane (col = lane & 31, half = lane >> 5), reg e -> row = (e & 3) + 8 * (e >> 2) + 4 * half
-    const int half = lane >> 5, kp32 = lane & 31;
-    const int cout8 = a.cout >> 3;
-    const bool addb = (d == 1);                              // trivial irrep: coefficient 0 carries sqrt(60) * bias
-        unsigned top = 0u;                                       // largest |coefficient| written (bit pattern; inf / NaN order above)
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, 0x7FFFFFFF, 0x00020000);
-#pragma unroll
-    for (int bi = 0; bi < 2; ++bi) {
-        const int tile32 = (kp0 >> 5) + bi;
-        if (tile32 >= a.nT32) continue;
-#pragma unroll
-        for (int ai = 0; ai < 4; ++ai) {
-            const int rowb = mtile * 256 + wm * 128 + ai * 32;     // the 32 rows of an MFMA tile share i (cout is a multiple of 32)
-            const int iidx = rowb / a.cout, o0 = rowb - iidx * a.cout;
-            if (iidx >= d) continue;
-            const int q = qbase + iidx * d + jidx;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int o = o0 + q4 * 8 + half * 4;
-                floatx4 val;
-                val.x = acc[ai][bi][4 * q4 + 0]; val.y = acc[ai][bi][4 * q4 + 1];
-                val.z = acc[ai][bi][4 * q4 + 2]; val.w = acc[ai][bi][4 * q4 + 3];
-                val *= a.descale;
-                if (addb) val += *reinterpret_cast<const floatx4*>(a.bias + o) * 7.745966692414834f;
-                const size_t off = (((((size_t)tile32 * G + q) * cout8 + (o >> 3)) * 2 + half) * TILE + kp32) * 4;
-                if (flags & F2_ST_SC1) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, val), orsrc, (int)(off * 4), 0, 16);
-                else if (flags & F2_ST_NT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uintx4, val), orsrc, (int)(off * 4), 0, 2);
-                else if (!(flags & F2_NOSTORE)) *reinterpret_cast<floatx4*>(a.out + off) = val;
-                top = max(max(top, __float_as_uint(val.x) & 0x7FFFFFFFu), __float_as_uint(val.y) & 0x7FFFFFFFu);
-                top = max(max(top, __float_as_uint(val.z) & 0x7FFFFFFFu), __float_as_uint(val.w) & 0x7FFFFFFFu);
-            }
-        }
-    }
-    note_range_bits(a.rflag, top, FP16_MAX / HF_ASCALE);     // the consumer multiplies by HF_ASCALE and converts to fp16
 }
 
+__global__ __launch_bounds__(512, 2) void fgemm3c_kernel(FGemmArgs a, int flags) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const Wave3 wv(__builtin_amdgcn_readfirstlane(tid >> 6), lane);
+    int t = 0, local = 0, r = 0;
+    if (!fg3_map(a, blockIdx.x & 7, blockIdx.x >> 3, t, local, r)) return;
+    const int d = a.dim[t];
+    const int MT = a.MT[t], KS = d * a.cin / 32, KT = 2 * KS;
+    const int cg = local / MT, mtile = local - cg * MT;
+    const int ntile = r + 8 * cg;
+    const char* Ag = a.A + a.a_off[t] + (size_t)mtile * KS * FG_STAGE;
+    const char* Bg = a.B + a.b_off[t] + (size_t)ntile * KS * FG_STAGE;
 
+    floatx16 acc[4][2];
+    zero_acc(acc);
+    const C8Scales sc(a.amax);
+    dma_step(wv.dm, Ag, Bg, smem);
+    dma_step(wv.dm, Ag + step_off(1), Bg + step_off(1), smem + F3_BUF);
+    const int row0 = mtile * 256 + wv.wm * 128, colbase = ntile * 256 + wv.nh * 128 + wv.wn * 64;
+    const bool rows_live = row0 < d * a.cout;       // else: all 128 rows of this wave are padding (cout = 32)
+    const int jidx = colbase / a.kppad, kp0 = colbase - jidx * a.kppad, qbase = a.qbase[t];
+    if ((flags & EPI_RES) && rows_live) residual_start(acc, row0, kp0, jidx, d, qbase, a.res, a.descale, a.cout, a.nT32, lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    ring_plain<true>(acc, smem, wv, Ag, [&](int s) { return Bg + step_off(s); }, KT, rows_live, sc);
+    if (rows_live) coef_epilogue(acc, row0, kp0, jidx, d, qbase, a.out, a.bias, a.descale, a.cout, a.nT32, a.rflag, lane, flags);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // cgemm (round 6): PartII's 13-element cone layer (utils/network.py:243-249,23-65 evaluated only where the g = 0 output needs it) as ONE
@@ -780,8 +521,7 @@ __global__ __launch_bounds__(512, 2) void cgemm_kernel(CGemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __shared__ int tapoff[16];
     const int tid = threadIdx.x, lane = tid & 63;
-    const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);             // 8 waves: waves 0-3 own the left 128 columns, 4-7 the right
-    const int w = w8 & 3;
+    const Wave3 wv(__builtin_amdgcn_readfirstlane(tid >> 6), lane);
     // work map: both row tiles of a column tile are neighbours on one XCD (the B panel is served from that XCD's L2 to the second one)
     const int xcd = blockIdx.x & 7, slot_ = blockIdx.x >> 3;
     const int ct = xcd + 8 * (slot_ / a.MT), mtile = slot_ % a.MT;
@@ -792,11 +532,6 @@ __global__ __launch_bounds__(512, 2) void cgemm_kernel(CGemmArgs a) {
     if (tid < 16) tapoff[tid] = tid < a.ntap ? (int)a.slot[j * 13 + tid] : 0;
     const char* Ag = a.A + (size_t)mtile * (KT / 2) * FG_STAGE;
     const char* Bt = a.B + (size_t)mt * a.nslot * a.KSt * FG_STAGE;      // this column tile's slots
-    const int nh = w8 >> 2;
-    const int wm = w >> 1, wn = w & 1;
-    const int wkg = w8 >> 2, wcb = w8 & 3;
-    const int la = wkg * 4096 + wcb * 1024 + lane * 16;
-    const int lb = la;
     __syncthreads();
     auto bsrc = [&](int s) -> const char* {
         const int tap = s / SPT, within = s - tap * SPT;
@@ -805,80 +540,15 @@ __global__ __launch_bounds__(512, 2) void cgemm_kernel(CGemmArgs a) {
     };
 
     floatx16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][jj][e] = 0.f;
-
+    zero_acc(acc);
     C8Scales sc;
-    sc.ah = 4.f; sc.al = 4.f / 2048.f; sc.bh = 1.f; sc.bl = 1.f; sc.mfma_b = 127;
-    if constexpr (FP8) {
-        const unsigned amax_bits = __builtin_amdgcn_readfirstlane(*a.amax);
-        int kexp = (int)(amax_bits >> 23) - 127 - 7;
-        kexp = kexp < -60 ? -60 : (kexp > 9 ? 9 : kexp);
-        sc.bh = __uint_as_float((unsigned)(kexp + 127) << 23); sc.bl = __uint_as_float((unsigned)(kexp - 11 + 127) << 23);
-        sc.mfma_b = 127 + kexp;
-    }
-    const int lane_a = (lane >> 5) * 4096 + (wm * 128 + (lane & 31)) * 16;
-    const int lane_b = 16384 + (lane >> 5) * 4096 + (nh * 128 + wn * 64 + (lane & 31)) * 16;
-
-    dma_step3(Ag, uniform_ptr(bsrc(0)), smem, la, lb, w, wkg, wcb);
-    dma_step3(Ag + step_off(1), uniform_ptr(bsrc(1)), smem + F3_BUF, la, lb, w, wkg, wcb);
+    if constexpr (FP8) sc = C8Scales(a.amax);
+    dma_step(wv.dm, Ag, uniform_ptr(bsrc(0)), smem);
+    dma_step(wv.dm, Ag + step_off(1), uniform_ptr(bsrc(1)), smem + F3_BUF);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
-    Frags8 c8;
-    if constexpr (FP8) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) c8.a[i][e] = 0;
-#pragma unroll
-        for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) c8.b[jj][e] = 0;
-    }
-    // fgemm3c's loop: step s lives in ring buffer s % 3; at its head the DMA of step s + 2 is issued into the buffer every wave finished
-    // reading before the barrier, the fragments of step s are read and the products issued; the two waves of a SIMD cover each other
-    int cur = 0, stg = 2 * F3_BUF;
-    int s = 0;
-    auto one_step = [&](auto parity) {
-        constexpr int PAR = decltype(parity)::value;
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        {
-            const int s2 = s + 2 < KT ? s + 2 : KT - 1;
-            dma_step3(uniform_ptr(Ag + step_off(s2)), uniform_ptr(bsrc(s2)), smem + stg, la, lb, w, wkg, wcb);
-        }
-        Frags2 f;
-        sfor<0, 12>([&](auto rc) { read_frag3<decltype(rc)::value>(smem + cur + lane_a, smem + cur + lane_b, f); });
-        if constexpr (FP8) step3c<PAR>(f, acc, c8, sc);
-        else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) acc[i][jj] = mfma_h(f.al[i], f.bh[jj], acc[i][jj]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) acc[i][jj] = mfma_h(f.ah[i], f.bl[jj], acc[i][jj]);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int jj = 0; jj < 2; ++jj) acc[i][jj] = mfma_h(f.ah[i], f.bh[jj], acc[i][jj]);
-        }
-        stg = cur;
-        cur = cur == 2 * F3_BUF ? 0 : cur + F3_BUF;
-        ++s;
-    };
-    for (int it = 0; it < KT; it += 2) {         // KT is even
-        one_step(std::integral_constant<int, 0>{});
-        one_step(std::integral_constant<int, 1>{});
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the re-staged tail pieces must not land in the LDS of the next workgroup
+    ring_plain<FP8>(acc, smem, wv, Ag, bsrc, KT, true, sc);            // cout % 256 == 0: no padding waves
 
     // ---- epilogue: D[row][col]: lane (col = lane & 31, half = lane >> 5), reg e -> row = (e & 3) + 8 * (e >> 2) + 4 * half.
     // v = acc * descale + bias; the next layer's BN + ReLU; x H2_ASCALE; hi / lo planes; 8 bytes (4 channels) per plane and lane
@@ -887,7 +557,7 @@ __global__ __launch_bounds__(512, 2) void cgemm_kernel(CGemmArgs a) {
     unsigned top = 0u;
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi) {
-        const int m = mt * 256 + nh * 128 + wn * 64 + bi * 32 + c32;     // match
+        const int m = mt * 256 + wv.nh * 128 + wv.wn * 64 + bi * 32 + c32;     // match
         // columns past the last 32-match tile were never written by the inverse transform (stale or foreign bytes): skipped before
         // they reach the range word, as in fgemm3c
         if ((m >> 5) >= a.nT32 || (m >> 4) >= a.nTiles16) continue;
@@ -895,7 +565,7 @@ __global__ __launch_bounds__(512, 2) void cgemm_kernel(CGemmArgs a) {
         for (int ai = 0; ai < 4; ++ai) {
 #pragma unroll
             for (int q4 = 0; q4 < 4; ++q4) {
-                const int o = mtile * 256 + wm * 128 + ai * 32 + q4 * 8 + half * 4;
+                const int o = mtile * 256 + wv.wm * 128 + ai * 32 + q4 * 8 + half * 4;
                 const floatx4 b4 = *reinterpret_cast<const floatx4*>(a.bias + o);
                 const floatx4 s4 = *reinterpret_cast<const floatx4*>(a.bn_s + o);
                 const floatx4 t4 = *reinterpret_cast<const floatx4*>(a.bn_t + o);
@@ -969,87 +639,42 @@ __device__ __forceinline__ void read_frag3s(const char* pa, const char* pb, Frag
 // One K16 step: 3 d MFMAs on `f` (lo.hi, hi.lo, hi.hi per accumulator, as fgemm3); behind them the 12 fragment reads of the next
 // step (rows beyond 32 d are padding: read, never used) and the wave's four DMA pieces of the step three ahead.
 template <bool DMA, int D>
-__device__ __forceinline__ void step3s(const Frags3s& f, floatx16 (&acc)[5], const char* ra, const char* rb, Frags3s& nf,
-                                       const char* srcA, const char* srcB, char* dmabuf, int la, int ldst) {
+__device__ __forceinline__ void step3s(const Frags3s& f, floatx16 (&acc)[5][1], const char* ra, const char* rb, Frags3s& nf,
+                                       const char* srcA, const char* srcB, char* dmabuf, const Dma3& dm) {
     sfor<0, 5>([&](auto gc) {
         constexpr int g = decltype(gc)::value;
-        if constexpr (g < D) acc[g] = mfma_h(f.al[g], f.bh, acc[g]);
+        if constexpr (g < D) acc[g][0] = mfma_h(f.al[g], f.bh, acc[g][0]);
         if constexpr (g < D) read_frag3s<g>(ra, rb, nf);
         if constexpr (g == 4) read_frag3s<5>(ra, rb, nf);
         __builtin_amdgcn_sched_barrier(0);
     });
     sfor<0, 5>([&](auto gc) {
         constexpr int g = decltype(gc)::value;
-        if constexpr (g < D) acc[g] = mfma_h(f.ah[g], f.bl, acc[g]);
+        if constexpr (g < D) acc[g][0] = mfma_h(f.ah[g], f.bl, acc[g][0]);
         if constexpr (g < D) read_frag3s<6 + g>(ra, rb, nf);
         if constexpr (g == 4) read_frag3s<11>(ra, rb, nf);
         __builtin_amdgcn_sched_barrier(0);
     });
     sfor<0, 5>([&](auto gc) {
         constexpr int g = decltype(gc)::value;
-        if constexpr (g < D) acc[g] = mfma_h(f.ah[g], f.bh, acc[g]);
-        if constexpr (DMA && g < 4) dma_piece3<g>(srcA, srcB, dmabuf, la, ldst);
+        if constexpr (g < D) acc[g][0] = mfma_h(f.ah[g], f.bh, acc[g][0]);
+        if constexpr (DMA && g < 4) dm.template piece<g>(srcA, srcB, dmabuf);
         __builtin_amdgcn_sched_barrier(0);
     });
 }
 
 // K loop of fgemm3s for an irrep of dimension D (compile time: no branches around the MFMAs, no reads of padding rows)
 template <int D>
-__device__ __forceinline__ void fgemm3s_kloop(floatx16 (&acc)[5], char* smem, const char* Ag, const char* Bg, int KT, int la, int ldst,
-                                              int lane_a, int lane_b) {
-    Frags3s P, Q;
+__device__ __forceinline__ void fgemm3s_kloop(floatx16 (&acc)[5][1], char* smem, const char* Ag, const char* Bg, int KT, const Dma3& dm, int lane_a, int lane_b) {
+    Frags3s P;
     sfor<0, 12>([&](auto rc) {
         constexpr int R = decltype(rc)::value;
         if constexpr (R == 5 || R == 11 || (R < 5 && R < D) || (R > 5 && R < 11 && R - 6 < D)) read_frag3s<R>(smem + lane_a, smem + lane_b, P);
     });
-    // Every wave must have step 0 in registers before ANY wave overwrites buffer 0 with step 3 (the first DMA of the loop below):
-    // inside the loop the barrier at the end of step s - 1 orders the reads of step s before the DMA of step s + 3, but between
-    // the prologue's barrier and the first step there was nothing - a wave delayed by a few hundred cycles (cold instruction
-    // cache at the head of a launch) read step 3's rows in place of step 0's.  Found in round 3 by the depth-first schedule
-    // (many short launches), whose outputs differed from the breadth-first pass in whole 32-keypoint wave tiles.
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    int cur = 0, nxt = F3_BUF;                   // ring offsets: step s lives in buffer s % 3
-    int s = 0;
-    auto advance = [&]() { cur = nxt; nxt = nxt == 2 * F3_BUF ? 0 : nxt + F3_BUF; ++s; };
-    auto sync4 = [] {
-        asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto sync0 = [] {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    // main loop: both steps of a pair still have a DMA to issue (s + 4 < KT)
-    while (s + 4 < KT) {
-        step3s<true, D>(P, acc, smem + nxt + lane_a, smem + nxt + lane_b, Q, uniform_ptr(Ag + step_off(s + 3)), uniform_ptr(Bg + step_off(s + 3)),
-                     smem + cur, la, ldst);
-        sync4();
-        advance();
-        step3s<true, D>(Q, acc, smem + nxt + lane_a, smem + nxt + lane_b, P, uniform_ptr(Ag + step_off(s + 3)), uniform_ptr(Bg + step_off(s + 3)),
-                     smem + cur, la, ldst);
-        sync4();
-        advance();
-    }
-    // tail: the last four steps (two if KT == 2); only the first of them still has a DMA (step KT - 1) to issue
-    if (KT >= 4) {
-        step3s<true, D>(P, acc, smem + nxt + lane_a, smem + nxt + lane_b, Q, uniform_ptr(Ag + step_off(s + 3)), uniform_ptr(Bg + step_off(s + 3)),
-                     smem + cur, la, ldst);
-        sync4();
-        advance();
-        step3s<false, D>(Q, acc, smem + nxt + lane_a, smem + nxt + lane_b, P, nullptr, nullptr, nullptr, la, ldst);
-        sync0();
-        advance();
-    }
-    step3s<false, D>(P, acc, smem + nxt + lane_a, smem + nxt + lane_b, Q, nullptr, nullptr, nullptr, la, ldst);
-    sync0();
-    advance();
-    // last step: its "next" fragments are read from a buffer that holds valid (unused) data
-    step3s<false, D>(Q, acc, smem + cur + lane_a, smem + cur + lane_b, P, nullptr, nullptr, nullptr, la, ldst);
-
+    ring_pipelined<F3_BUF, 4>(smem, Ag, Bg, KT, lane_a, lane_b, P,
+        [&](auto dmac, const Frags3s& f, Frags3s& nf, const char* ra, const char* rb, const char* srcA, const char* srcB, char* buf) {
+            step3s<decltype(dmac)::value, D>(f, acc, ra, rb, nf, srcA, srcB, buf, dm);
+        });
 }
 
 __global__ __launch_bounds__(512, 2) void fgemm3s_kernel(FGemmArgs a, int flags) {
@@ -1058,71 +683,31 @@ __global__ __launch_bounds__(512, 2) void fgemm3s_kernel(FGemmArgs a, int flags)
     const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
     int t = 0, local = 0, r = 0;
     if (!fg3_map(a, blockIdx.x & 7, blockIdx.x >> 3, t, local, r)) return;
-    const int d = a.dim[t], qbase = a.qbase[t];
+    const int d = a.dim[t];
     const int KS = d * a.cin / 32, KT = 2 * KS;                        // MT = 1: the tile holds all 32 d rows
     const int ntile = r + 8 * local;
     const char* Ag = a.A + a.a_off[t];
     const char* Bg = a.B + a.b_off[t] + (size_t)ntile * KS * FG_STAGE;
-    const int wkg = w8 >> 2, wcb = w8 & 3;                               // this wave's DMA pieces: k-group, 64-row / 64-column block
-    const int la = wkg * 4096 + wcb * 1024 + lane * 16;
-    const int ldst = wkg * 4096 + wcb * 1024;
-
-    floatx16 acc[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
-
+    const Dma3 dm(w8, lane);
     const int lane_a = (lane >> 5) * 4096 + (lane & 31) * 16;
     const int lane_b = 16384 + (lane >> 5) * 4096 + (w8 * 32 + (lane & 31)) * 16;
 
-    auto dma = [&](int st, char* buf) {
-        const char* sa = uniform_ptr(Ag + step_off(st));
-        const char* sb = uniform_ptr(Bg + step_off(st));
-        sfor<0, 4>([&](auto uc) { dma_piece3<decltype(uc)::value>(sa, sb, buf, la, ldst); });
-    };
-    dma(0, smem);
-    dma(1, smem + F3_BUF);
-    if (KT > 2) dma(2, smem + 2 * F3_BUF);
+    floatx16 acc[5][1];
+    zero_acc(acc);
+    ring_prologue<F3_BUF>(KT, [&](int st, int buf) { dma_step(dm, uniform_ptr(Ag + step_off(st)), uniform_ptr(Bg + step_off(st)), smem + buf); });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
     switch (d) {
-        case 1: fgemm3s_kloop<1>(acc, smem, Ag, Bg, KT, la, ldst, lane_a, lane_b); break;
-        case 3: fgemm3s_kloop<3>(acc, smem, Ag, Bg, KT, la, ldst, lane_a, lane_b); break;
-        case 4: fgemm3s_kloop<4>(acc, smem, Ag, Bg, KT, la, ldst, lane_a, lane_b); break;
-        default: fgemm3s_kloop<5>(acc, smem, Ag, Bg, KT, la, ldst, lane_a, lane_b); break;
+        case 1: fgemm3s_kloop<1>(acc, smem, Ag, Bg, KT, dm, lane_a, lane_b); break;
+        case 3: fgemm3s_kloop<3>(acc, smem, Ag, Bg, KT, dm, lane_a, lane_b); break;
+        case 4: fgemm3s_kloop<4>(acc, smem, Ag, Bg, KT, dm, lane_a, lane_b); break;
+        default: fgemm3s_kloop<5>(acc, smem, Ag, Bg, KT, dm, lane_a, lane_b); break;
     }
-
-    // ---- epilogue: D[row][col]: lane (col = lane & 31, half = lane >> 5), reg e -> row = (e & 3) + 8 * (e >> 2) + 4 * half
-    const int half = lane >> 5, kp32 = lane & 31;
-    const int cout8 = a.cout >> 3;                                       // = 4: row tile ai is coefficient row i = ai
-    const bool addb = (d == 1);                                          // trivial irrep: coefficient 0 carries sqrt(60) * bias
+    // 32 output channels (launch_fgemm3): row tile ai of the wave is coefficient row i = ai; the experiments build honours `nostore` alone here
     const int colbase = ntile * 256 + w8 * 32;
     const int jidx = colbase / a.kppad, kp0 = colbase - jidx * a.kppad;
-    const int tile32 = kp0 >> 5;
-    unsigned top = 0u;
-    if (tile32 < a.nT32) {
-#pragma unroll
-        for (int ai = 0; ai < 5; ++ai) {
-            if (ai >= d) continue;
-            const int q = qbase + ai * d + jidx;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int o = q4 * 8 + half * 4;
-                floatx4 val;
-                val.x = acc[ai][4 * q4 + 0]; val.y = acc[ai][4 * q4 + 1];
-                val.z = acc[ai][4 * q4 + 2]; val.w = acc[ai][4 * q4 + 3];
-                val *= a.descale;
-                if (addb) val += *reinterpret_cast<const floatx4*>(a.bias + o) * 7.745966692414834f;
-                const size_t off = (((((size_t)tile32 * G + q) * cout8 + (o >> 3)) * 2 + half) * TILE + kp32) * 4;
-                if (!(flags & F2_NOSTORE)) *reinterpret_cast<floatx4*>(a.out + off) = val;
-                top = max(max(top, __float_as_uint(val.x) & 0x7FFFFFFFu), __float_as_uint(val.y) & 0x7FFFFFFFu);
-                top = max(max(top, __float_as_uint(val.z) & 0x7FFFFFFFu), __float_as_uint(val.w) & 0x7FFFFFFFu);
-            }
-        }
-    }
-    note_range_bits(a.rflag, top, FP16_MAX / HF_ASCALE);
+    coef_epilogue(acc, 0, kp0, jidx, d, a.qbase[t], a.out, a.bias, a.descale, 32, a.nT32, a.rflag, lane, flags & F2_NOSTORE);
 }
 
 int fgemm3_init() {
@@ -1138,16 +723,7 @@ int launch_fgemm3(const FGemmArgs& a, int flags, hipStream_t s) {
         if (std::strstr(dbg, "sc1")) flags |= F2_ST_SC1;            // round 6: the coefficient stores write-through ...
         if (std::strstr(dbg, "stnt")) flags |= F2_ST_NT;            // ... or non-temporal: produced once, consumed once by gft16x
     }
-    int tot = 0;
-    for (int x = 0; x < 8; ++x) {
-        int n = 0;
-        for (int t = 0; t < NIR_ORD; ++t) {
-            const int r = (x + a.rot[t]) & 7;
-            if (a.NT[t] > r) n += ((a.NT[t] - 1 - r) / 8 + 1) * a.MT[t];
-        }
-        tot = n > tot ? n : tot;
-    }
-    tot *= 8;
+    const int tot = fgemm_grid(a, 1);
     // 32 output channels, no residual: all 32 d live rows in every wave (fgemm3s); YOHO_FGEMM_DEBUG=nosmall keeps fgemm3
     static const bool small_ok = [] { const char* e = experiment_env("YOHO_FGEMM_DEBUG"); return !(e && std::strstr(e, "nosmall")); }();
     if (small_ok && a.cout == 32 && !(flags & EPI_RES)) hipLaunchKernelGGL(fgemm3s_kernel, dim3(tot), dim3(512), F3_LDS, s, a, flags);
@@ -1171,17 +747,7 @@ int launch_fgemm2(const FGemmArgs& a, int flags, hipStream_t s) {
         if (std::strstr(dbg, "sparse4")) flags |= F2_SPARSE4;
         if (std::strstr(dbg, "sparse16")) flags |= F2_SPARSE16;
     }
-    int tot = 0;
-    for (int x = 0; x < 8; ++x) {
-        int n = 0;
-        for (int t = 0; t < NIR_ORD; ++t) {
-            const int r = (x + a.rot[t]) & 7;
-            if (a.NT[t] > r) n += ((a.NT[t] - 1 - r) / 8 + 1) * a.MT[t] * 2;
-        }
-        tot = n > tot ? n : tot;
-    }
-    tot *= 8;
-    hipLaunchKernelGGL(fgemm2_kernel, dim3(tot), dim3(256), F2_LDS, s, a, flags);
+    hipLaunchKernelGGL(fgemm2_kernel, dim3(fgemm_grid(a, 2)), dim3(256), F2_LDS, s, a, flags);
     HIPCHK(hipGetLastError());
     return 0;
 }
