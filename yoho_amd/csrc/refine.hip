@@ -6,6 +6,7 @@
 //   rf_icp_pair_kernel                                           ICP: transform + the same walk + gate + first-pass partial sums
 //   rf_refit_mask_kernel                                         refit: estim.hip's inlier() + first-pass partial sums
 //   rf_mean_kernel / rf_*_cov_kernel / rf_solve_kernel           the Kabsch step: centroids, centred products, Jacobi, stop word
+// The device-side pieces of the grid and of the sums (rf_cell, rf_slot, rf_walk, rf_block_sum) are in rfgrid.h, which plane.hip shares.
 //
 // THE GRID.  gridnn.hip's grid (linked lists behind an open-addressing table, a wave and 125 probes per query, brute force for what it
 // cannot settle) is built for queries that all have a partner nearby; in ICP half the cloud has none.  Here the targets are SORTED by
@@ -58,39 +59,14 @@
 // the limit - and rf_scan_kernel is one workgroup scanning 256 nblk counts, two or three times per grid build.  That is the price of the
 // stated summation order with the simplest kernels; a two-level version (per-thread partial runs in block order, combined in order) keeps
 // the order and is the remedy if the 300 000-point timing asks for it.  Timings: tools/time_refine.py -> profiles/refine.md.
-#include "common.h"
-#include "nnmath.h"
+#include "rfgrid.h"
 #include "yoho_refine.h"
 #include <cmath>
 
 namespace yoho {
 
-typedef unsigned long long u64;
-constexpr int RF_CLAMP = (1 << 20) - 1;
-constexpr int RF_NONE = 0x7FFFFFFF;
 constexpr int RF_SLAB = 16;          // doubles per slab row (8 or 9 used)
-constexpr double RF_MIN_CELL = 0x1p-60;
 constexpr double RF_RANK_TOL = 1e-13;
-
-// gridnn.hip's gn_cell / gn_key / gn_slot
-__device__ __forceinline__ int rf_cell(double x, double inv_cell) {
-    double c = floor(x * inv_cell);
-    c = fmin(fmax(c, -(double)RF_CLAMP), (double)RF_CLAMP);          // NaN -> -RF_CLAMP
-    return (int)c;
-}
-__device__ __forceinline__ int rf_clampi(int c) { return c < -RF_CLAMP ? -RF_CLAMP : (c > RF_CLAMP ? RF_CLAMP : c); }
-__device__ __forceinline__ unsigned rf_slot(int cx, int cy, int cz, unsigned mask) {
-    const u64 key = ((u64)(unsigned)(cx + (1 << 20)) << 42) | ((u64)(unsigned)(cy + (1 << 20)) << 21) | (u64)(unsigned)(cz + (1 << 20));
-    return (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 33) & mask;
-}
-
-struct RfGrid {
-    const int* start;        // [nslots + 1] first sorted position of a bucket
-    const float4* pk;        // [Nt] sorted points (x, y, z, original index)
-    double inv_cell;
-    unsigned mask;           // nslots - 1
-    float gate2;
-};
 
 // ---- the sort ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rf_key_kernel(const float* __restrict__ pts, int n, double inv_cell, unsigned mask, unsigned* __restrict__ keys,
@@ -184,24 +160,7 @@ __global__ __launch_bounds__(256) void rf_cells_kernel(const unsigned* __restric
     }
 }
 
-// ---- the query -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void rf_walk(const RfGrid& g, const float (&q)[3], float& bd, int& bi) {
-    const int cx = rf_cell((double)q[0], g.inv_cell), cy = rf_cell((double)q[1], g.inv_cell), cz = rf_cell((double)q[2], g.inv_cell);
-    bd = __builtin_inff();
-    bi = RF_NONE;
-    for (int c = 0; c < 27; ++c) {
-        const unsigned s = rf_slot(rf_clampi(cx + c % 3 - 1), rf_clampi(cy + (c / 3) % 3 - 1), rf_clampi(cz + c / 9 - 1), g.mask);
-        const int p1 = g.start[s + 1];
-        for (int p = g.start[s]; p < p1; ++p) {
-            const float4 v = g.pk[p];
-            const float b[3] = {v.x, v.y, v.z};
-            const float d2 = dist2_f32<3>(q, b);
-            const int j = __float_as_int(v.w);
-            if (d2 < g.gate2 && (d2 < bd || (d2 == bd && j < bi))) { bd = d2; bi = j; }
-        }
-    }
-}
-
+// ---- the query (rf_walk: rfgrid.h) -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rf_within_kernel(RfGrid g, const float* __restrict__ q, int Nq, int64_t* __restrict__ idx, float* __restrict__ d2) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Nq) return;
@@ -223,25 +182,6 @@ struct RfState {
     int best, best_count;    // refit: the iterate with the largest count so far
     int evaluated, pad;
 };
-
-template <int NV>
-__device__ __forceinline__ void rf_block_sum(double (&v)[NV], double* __restrict__ slab_row) {
-    __shared__ double red[4][NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v[k] = __dadd_rn(v[k], __shfl_xor(v[k], o));
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) red[threadIdx.x >> 6][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        const int k = threadIdx.x;
-        slab_row[k] = __dadd_rn(__dadd_rn(__dadd_rn(red[0][k], red[1][k]), red[2][k]), red[3][k]);
-    }
-}
 
 __global__ void rf_init_kernel(RfState* __restrict__ st, const double* __restrict__ T_in, double* __restrict__ Tall, int32_t* __restrict__ ints, int nints,
                                double* __restrict__ dbls, int ndbls) {
@@ -496,13 +436,7 @@ __global__ void rf_finish_kernel(const RfState* __restrict__ st, const double* _
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-struct RfGridWs {
-    unsigned nslots; int bits, nblk;
-    unsigned* keys[2]; int* idx[2];
-    int* hist; int* start; float4* pk;
-};
-
-static void rf_grid_layout(Arena& ar, int Nt, RfGridWs& w) {
+void rf_grid_layout(Arena& ar, int Nt, RfGridWs& w) {
     w.bits = 8;
     while (w.bits < 23 && (1u << w.bits) < 2u * (unsigned)Nt) ++w.bits;
     w.nslots = 1u << w.bits;
@@ -513,7 +447,7 @@ static void rf_grid_layout(Arena& ar, int Nt, RfGridWs& w) {
     w.pk = ar.take<float4>((size_t)Nt);
 }
 
-static int rf_build_grid(const float* tgt, int Nt, float max_dist, const RfGridWs& w, RfGrid& g, hipStream_t s) {
+int rf_build_grid(const float* tgt, int Nt, float max_dist, const RfGridWs& w, RfGrid& g, hipStream_t s) {
     double cell = (double)max_dist * (1.0 + 0x1p-10);
     if (cell < RF_MIN_CELL) cell = RF_MIN_CELL;
     g.inv_cell = 1.0 / cell;
@@ -539,8 +473,6 @@ static int rf_build_grid(const float* tgt, int Nt, float max_dist, const RfGridW
     HIPCHK(hipGetLastError());
     return 0;
 }
-
-static bool rf_bad_radius(float r) { return !(r > 0.f) || !std::isfinite(r); }
 
 }  // namespace yoho
 

@@ -1,4 +1,4 @@
-"""ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h, include/yoho_refine.h) + a thin tensor-level wrapper.
+"""ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h, include/yoho_refine.h, include/yoho_plane.h) + a thin tensor-level wrapper.
 
 PyTorch-ROCm tensors are the device-memory container only: every method passes
 ``tensor.data_ptr()`` and the current HIP stream to the C ABI.  There is NO CPU fallback: if the
@@ -41,6 +41,8 @@ REFINE_MAX_POINTS = 1 << 22                 # YOHO_REFINE_MAX_POINTS
 REFIT_MAX_ITERS = 32                        # YOHO_REFIT_MAX_ITERS
 ICP_MAX_ITERS = 64                          # YOHO_ICP_MAX_ITERS
 ICP_REASONS = ("iters", "converged", "few_pairs", "rank")      # YOHO_ICP_ITERS .. YOHO_ICP_RANK
+# the entries of include/yoho_plane.h (normals and point-to-plane ICP), kept apart for the same reason; they reuse the limits and reasons above
+PLANE_SYMBOLS = ["yoho_estimate_normals", "yoho_icp_plane"]
 
 
 class ConvW(C.Structure):
@@ -86,7 +88,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -146,7 +148,9 @@ def load_library():
     lib.yoho_nn_within.argtypes = [vp, vp, ci, vp, ci, C.c_float, vp, vp, vp]
     lib.yoho_refit_matches.argtypes = [vp, vp, vp, ci, vp, C.c_double, ci, vp, vp, vp, vp]
     lib.yoho_icp_refine.argtypes = [vp, vp, ci, vp, ci, vp, C.c_float, ci, C.c_double, vp, vp, vp, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS:
+    lib.yoho_estimate_normals.argtypes = [vp, vp, ci, C.c_float, ci, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp]
+    lib.yoho_icp_plane.argtypes = [vp, vp, ci, vp, ci, vp, vp, C.c_float, ci, C.c_double, vp, vp, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -672,6 +676,39 @@ class Context:
                                          _dev(T, torch.float64, "T"), float(max_dist), iters, float(tol), C.c_void_p(T_out.data_ptr()),
                                          C.c_void_p(npairs.data_ptr()) if iters > 0 else None, C.c_void_p(rmse.data_ptr()) if iters > 0 else None,
                                          C.c_void_p(info.data_ptr()), _stream()))
+        return T_out, npairs, rmse, info
+
+    # ---- normals and point-to-plane ICP (include/yoho_plane.h) -------------------------------
+    def estimate_normals(self, pts, radius, min_nbrs=6, viewpoint=(0, 0, 0), want_curv=False):
+        """pts (N,3) f32 -> (normals (N,3) f32, count (N) int32[, curv (N) f32]), device tensors: the unit eigenvector of the smallest
+        eigenvalue of the f64 covariance of the neighbours inside `radius` (the point itself included; count = their number), turned
+        towards `viewpoint`; (0, 0, 0) and curv -1 where count < min_nbrs or the neighbours are collinear (yoho_estimate_normals)."""
+        if pts.dim() != 2 or pts.shape[1] != 3 or len(viewpoint) != 3:
+            raise ValueError("estimate_normals: pts (N,3), viewpoint (3)")
+        N = pts.shape[0]
+        normals = torch.empty((N, 3), dtype=torch.float32, device=pts.device)
+        count = torch.empty((N,), dtype=torch.int32, device=pts.device)
+        curv = torch.empty((N,), dtype=torch.float32, device=pts.device) if want_curv else None
+        _check(self._lib.yoho_estimate_normals(self._h, _dev(pts, torch.float32, "pts"), N, float(radius), int(min_nbrs), float(viewpoint[0]),
+                                               float(viewpoint[1]), float(viewpoint[2]), C.c_void_p(normals.data_ptr()), C.c_void_p(count.data_ptr()),
+                                               C.c_void_p(curv.data_ptr()) if want_curv else None, _stream()))
+        return (normals, count, curv) if want_curv else (normals, count)
+
+    def icp_plane(self, src, tgt, tgt_normals, T, max_dist, iters=30, tol=0.0):
+        """src (Ns,3), tgt (Nt,3), tgt_normals (Nt,3) f32, T (3,4) f64 on the device mapping src onto tgt -> icp_refine's tuple (T_out,
+        npairs, rmse, info), device tensors: gated point-to-plane ICP (yoho_icp_plane); rmse is the point-to-plane rms in front of
+        every step, a pair whose target normal is (0, 0, 0) or not finite is not kept."""
+        if src.dim() != 2 or tgt.dim() != 2 or src.shape[1] != 3 or tgt.shape[1] != 3 or tuple(tgt_normals.shape) != tuple(tgt.shape) or T.numel() != 12:
+            raise ValueError("icp_plane: src (Ns,3), tgt (Nt,3), tgt_normals (Nt,3), T (3,4)")
+        iters = int(iters)
+        T_out = torch.empty((3, 4), dtype=torch.float64, device=T.device)
+        npairs = torch.empty((max(iters, 0),), dtype=torch.int32, device=T.device)
+        rmse = torch.empty((max(iters, 0),), dtype=torch.float64, device=T.device)
+        info = torch.empty((2,), dtype=torch.int32, device=T.device)
+        _check(self._lib.yoho_icp_plane(self._h, _dev(src, torch.float32, "src"), src.shape[0], _dev(tgt, torch.float32, "tgt"), tgt.shape[0],
+                                        _dev(tgt_normals, torch.float32, "tgt_normals"), _dev(T, torch.float64, "T"), float(max_dist), iters, float(tol),
+                                        C.c_void_p(T_out.data_ptr()), C.c_void_p(npairs.data_ptr()) if iters > 0 else None,
+                                        C.c_void_p(rmse.data_ptr()) if iters > 0 else None, C.c_void_p(info.data_ptr()), _stream()))
         return T_out, npairs, rmse, info
 
     def mutual_nn(self, a, b):

@@ -31,7 +31,8 @@ def describe_pair(ctx, feat0, feat1, check_range=True):
 
 
 def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, order_rng=None, eqv=None, estimator="yohoo", seed=0,
-             hypotheses="all", refine=None, refine_iters=4, clouds=None, max_dist=None, icp_iters=30):
+             hypotheses="all", refine=None, refine_iters=4, clouds=None, max_dist=None, icp_iters=30,
+             normal_radius=None):
     """feat0/feat1 (K,32,60) f32 cuda (FCGF group features), keys0/keys1 (K,3) f64 cuda.
     estimator 'yohoo' (tests/evaluator.py:112-117: PartII + one-shot vote over <= max_iter per-match hypotheses, order
     shuffled by order_rng) or 'yohoc' (tests/evaluator.py:41-47: max_iter Kabsch RANSAC iterations sampled on the device
@@ -44,20 +45,22 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
     which other matches share its pass), the other M - H hypotheses - which nothing downstream of the vote reads - are not computed.
     refine: None (default) = the estimator's transform is the result, nothing else runs; "refit" = the winner refitted on its inlier
     matches (refine.refine_pair, refine_iters iterations); "refit+icp" = then polished by icp_iters iterations of gated ICP of
-    clouds = (cloud0, cloud1), (N,3) f32 cuda, inside max_dist.  Every field above stays what it is without refinement; trans_refined
+    clouds = (cloud0, cloud1), (N,3) f32 cuda, inside max_dist; "refit+icp_plane" = the same with point-to-plane ICP on cloud0's
+    normals, estimated inside normal_radius (None: max_dist).  Every field above stays what it is without refinement; trans_refined
     (3,4) and refine (refine_pair's dict) are added - None when no hypothesis has an inlier."""
-    if refine not in (None, "refit", "refit+icp"):
-        raise ValueError(f"refine must be None, 'refit' or 'refit+icp', got {refine!r}")
-    if refine == "refit+icp" and (clouds is None or max_dist is None):
-        raise ValueError("refine='refit+icp' needs clouds=(cloud0, cloud1) and max_dist")
+    if refine not in (None, "refit", "refit+icp", "refit+icp_plane"):
+        raise ValueError(f"refine must be None, 'refit', 'refit+icp' or 'refit+icp_plane', got {refine!r}")
+    with_icp = refine in ("refit+icp", "refit+icp_plane")
+    if with_icp and (clouds is None or max_dist is None):
+        raise ValueError(f"refine={refine!r} needs clouds=(cloud0, cloud1) and max_dist")
     r = PairResult()
     r.trans_refined = r.refine = None
 
     def refined(T_dev):
         # the winner's transform is still on the device: it chains into the refit without another host read in front
         from .refine import refine_pair
-        r.refine = refine_pair(ctx, keys0, keys1, r.match, T_dev, inlier_dist, iters=refine_iters, clouds=clouds if refine == "refit+icp" else None,
-                               max_dist=max_dist, icp_iters=icp_iters)
+        r.refine = refine_pair(ctx, keys0, keys1, r.match, T_dev, inlier_dist, iters=refine_iters, clouds=clouds if with_icp else None,
+                               max_dist=max_dist, icp_iters=icp_iters, icp="plane" if refine == "refit+icp_plane" else "point", normal_radius=normal_radius)
         r.trans_refined = r.refine["trans"]
 
     r.range_repeats = 0
