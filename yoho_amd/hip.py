@@ -43,6 +43,9 @@ ICP_MAX_ITERS = 64                          # YOHO_ICP_MAX_ITERS
 ICP_REASONS = ("iters", "converged", "few_pairs", "rank")      # YOHO_ICP_ITERS .. YOHO_ICP_RANK
 # the entries of include/yoho_plane.h (normals and point-to-plane ICP), kept apart for the same reason; they reuse the limits and reasons above
 PLANE_SYMBOLS = ["yoho_estimate_normals", "yoho_icp_plane"]
+# the entries of include/yoho_verify.h (hypotheses verified on the clouds), kept apart for the same reason
+VERIFY_SYMBOLS = ["yoho_eval_transforms", "yoho_verify_hypotheses"]
+VERIFY_MAX_K = 64                           # YOHO_VERIFY_MAX_K
 
 
 class ConvW(C.Structure):
@@ -88,7 +91,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -150,7 +153,9 @@ def load_library():
     lib.yoho_icp_refine.argtypes = [vp, vp, ci, vp, ci, vp, C.c_float, ci, C.c_double, vp, vp, vp, vp, vp]
     lib.yoho_estimate_normals.argtypes = [vp, vp, ci, C.c_float, ci, C.c_float, C.c_float, C.c_float, vp, vp, vp, vp]
     lib.yoho_icp_plane.argtypes = [vp, vp, ci, vp, ci, vp, vp, C.c_float, ci, C.c_double, vp, vp, vp, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS:
+    lib.yoho_eval_transforms.argtypes = [vp, vp, ci, vp, ci, vp, ci, C.c_float, vp, vp, vp, vp]
+    lib.yoho_verify_hypotheses.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, C.c_double, C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -710,6 +715,52 @@ class Context:
                                         C.c_void_p(T_out.data_ptr()), C.c_void_p(npairs.data_ptr()) if iters > 0 else None,
                                         C.c_void_p(rmse.data_ptr()) if iters > 0 else None, C.c_void_p(info.data_ptr()), _stream()))
         return T_out, npairs, rmse, info
+
+    # ---- hypotheses verified on the clouds (include/yoho_verify.h) ---------------------------
+    def eval_transforms(self, src, tgt, T, max_dist):
+        """src (Ns,3), tgt (Nt,3) f32 clouds, T (K,3,4) f64 on the device, every row mapping src onto tgt, 1 <= K <= VERIFY_MAX_K ->
+        (npairs (K) int32, rmse (K) f64, cost (K) f64), device tensors: per row the source points with a partner inside max_dist, their
+        rms distance (+inf without a pair) and the truncated cost SUM(paired ? d2 : max_dist^2) (yoho_eval_transforms); one grid
+        build for all rows."""
+        if src.dim() != 2 or tgt.dim() != 2 or src.shape[1] != 3 or tgt.shape[1] != 3 or T.dim() != 3 or tuple(T.shape[1:]) != (3, 4):
+            raise ValueError("eval_transforms: src (Ns,3), tgt (Nt,3), T (K,3,4)")
+        K = T.shape[0]
+        npairs = torch.empty((K,), dtype=torch.int32, device=T.device)
+        rmse = torch.empty((K,), dtype=torch.float64, device=T.device)
+        cost = torch.empty((K,), dtype=torch.float64, device=T.device)
+        _check(self._lib.yoho_eval_transforms(self._h, _dev(src, torch.float32, "src"), src.shape[0], _dev(tgt, torch.float32, "tgt"), tgt.shape[0],
+                                              _dev(T, torch.float64, "T") if K else None, K, float(max_dist), C.c_void_p(npairs.data_ptr()),
+                                              C.c_void_p(rmse.data_ptr()), C.c_void_p(cost.data_ptr()), _stream()))
+        return npairs, rmse, cost
+
+    def verify_hypotheses(self, src, tgt, T, counts, K, max_dist, order=None, min_count=1, distinct_tol=0.0):
+        """src (Ns,3), tgt (Nt,3) f32 clouds, T (.,3,4) f64 hypotheses, counts (H) int32 and order (H) int64 or None as o_score took /
+        left them (position h = hypothesis T[order[h]] with counts[h] inliers), all on the device -> (T_out (3,4) f64, top (K) int32,
+        npairs (K) int32, rmse (K) f64, cost (K) f64, info int32[4] = (Kc, best, top[best], counts[top[best]])), device tensors: the K
+        positions with the most inliers among those with at least min_count - hypotheses within distinct_tol of one already taken
+        are skipped -, each evaluated as eval_transforms does, T_out the one with the smallest cost (yoho_verify_hypotheses); rows
+        behind Kc hold -1, T_out = [I|0] when Kc = 0.  T_out chains into refit_matches / icp_refine / icp_plane."""
+        if src.dim() != 2 or tgt.dim() != 2 or src.shape[1] != 3 or tgt.shape[1] != 3 or T.dim() != 3 or tuple(T.shape[1:]) != (3, 4) or counts.dim() != 1:
+            raise ValueError("verify_hypotheses: src (Ns,3), tgt (Nt,3), T (.,3,4), counts (H)")
+        H, K = counts.shape[0], int(K)
+        if order is not None and tuple(order.shape) != (H,):
+            raise ValueError("verify_hypotheses: order must have one entry per count")
+        if order is None and T.shape[0] < H:
+            raise ValueError("verify_hypotheses: without an order T needs a row per count")
+        dev = src.device
+        T_out = torch.empty((3, 4), dtype=torch.float64, device=dev)
+        top = torch.empty((max(K, 0),), dtype=torch.int32, device=dev)
+        npairs = torch.empty((max(K, 0),), dtype=torch.int32, device=dev)
+        rmse = torch.empty((max(K, 0),), dtype=torch.float64, device=dev)
+        cost = torch.empty((max(K, 0),), dtype=torch.float64, device=dev)
+        info = torch.empty((4,), dtype=torch.int32, device=dev)
+        _check(self._lib.yoho_verify_hypotheses(self._h, _dev(src, torch.float32, "src"), src.shape[0], _dev(tgt, torch.float32, "tgt"), tgt.shape[0],
+                                                _dev(T, torch.float64, "T") if H else None,
+                                                _dev(order, torch.int64, "order") if (order is not None and H) else None,
+                                                _dev(counts, torch.int32, "counts") if H else None, H, K, int(min_count), float(distinct_tol),
+                                                float(max_dist), C.c_void_p(T_out.data_ptr()), C.c_void_p(top.data_ptr()), C.c_void_p(npairs.data_ptr()),
+                                                C.c_void_p(rmse.data_ptr()), C.c_void_p(cost.data_ptr()), C.c_void_p(info.data_ptr()), _stream()))
+        return T_out, top, npairs, rmse, cost, info
 
     def mutual_nn(self, a, b):
         """a (Na,32), b (Nb,32) -> (M,2) int64 mutual nearest neighbours, ascending in a."""

@@ -16,7 +16,7 @@ import torch
 
 class PairResult:
     __slots__ = ("match", "dr_index", "quat", "trans_pre", "best_h", "best_count", "trans", "order", "eqv", "range_repeats", "hyp_rows", "matches",
-                 "trans_refined", "refine")
+                 "trans_refined", "refine", "trans_verified", "verify")
 
 
 def describe_pair(ctx, feat0, feat1, check_range=True):
@@ -32,7 +32,7 @@ def describe_pair(ctx, feat0, feat1, check_range=True):
 
 def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, order_rng=None, eqv=None, estimator="yohoo", seed=0,
              hypotheses="all", refine=None, refine_iters=4, clouds=None, max_dist=None, icp_iters=30,
-             normal_radius=None):
+             normal_radius=None, verify=None, verify_dist=None, verify_distinct=0.0, verify_min_count=1):
     """feat0/feat1 (K,32,60) f32 cuda (FCGF group features), keys0/keys1 (K,3) f64 cuda.
     estimator 'yohoo' (tests/evaluator.py:112-117: PartII + one-shot vote over <= max_iter per-match hypotheses, order
     shuffled by order_rng) or 'yohoc' (tests/evaluator.py:41-47: max_iter Kabsch RANSAC iterations sampled on the device
@@ -47,14 +47,28 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
     matches (refine.refine_pair, refine_iters iterations); "refit+icp" = then polished by icp_iters iterations of gated ICP of
     clouds = (cloud0, cloud1), (N,3) f32 cuda, inside max_dist; "refit+icp_plane" = the same with point-to-plane ICP on cloud0's
     normals, estimated inside normal_radius (None: max_dist).  Every field above stays what it is without refinement; trans_refined
-    (3,4) and refine (refine_pair's dict) are added - None when no hypothesis has an inlier."""
+    (3,4) and refine (refine_pair's dict) are added - None when no hypothesis has an inlier.
+    verify: None (default) = nothing else runs, trans_verified and verify are None; K (1 .. hip.VERIFY_MAX_K, YOHO-O only) = the K
+    vote positions with the most inliers (at least verify_min_count; hypotheses within verify_distinct of one already taken, largest
+    entry difference, are skipped) are evaluated on clouds = (cloud0, cloud1) - without clouds on the keypoint sets themselves, keys1
+    onto keys0, cast to f32 - inside verify_dist (None: inlier_dist), and the one with the smallest truncated cost is kept
+    (Context.verify_hypotheses, include/yoho_verify.h).  trans, best_h and best_count stay the vote's; trans_verified (3,4) is that
+    hypothesis ([I|0] when no position qualifies) and verify = dict(top, counts (of the positions in top), npairs, rmse, cost (K; -1
+    behind the rows taken), best (row, -1 when none), fitness = npairs[best] / Ns), fetched in one additional host read.  With refine
+    as well the refinement starts from the verified transform, chained in on the device."""
     if refine not in (None, "refit", "refit+icp", "refit+icp_plane"):
         raise ValueError(f"refine must be None, 'refit', 'refit+icp' or 'refit+icp_plane', got {refine!r}")
+    if verify is not None:
+        if estimator == "yohoc":
+            raise ValueError("verify needs estimator='yohoo': yoho_c_ransac_device keeps only its winner, there is nothing to choose from")
+        from .hip import VERIFY_MAX_K
+        if int(verify) != verify or not 1 <= verify <= VERIFY_MAX_K:
+            raise ValueError(f"verify must be None or an integer in [1, {VERIFY_MAX_K}], got {verify!r}")
     with_icp = refine in ("refit+icp", "refit+icp_plane")
     if with_icp and (clouds is None or max_dist is None):
         raise ValueError(f"refine={refine!r} needs clouds=(cloud0, cloud1) and max_dist")
     r = PairResult()
-    r.trans_refined = r.refine = None
+    r.trans_refined = r.refine = r.trans_verified = r.verify = None
 
     def refined(T_dev):
         # the winner's transform is still on the device: it chains into the refit without another host read in front
@@ -115,6 +129,8 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
         vote_order = torch.arange(H, dtype=torch.int64, device=feat0.device)
         r.hyp_rows = sel_d
 
+    vote = {}                                              # counts / order / H of the vote as last run, for the verification
+
     def head_and_vote():
         # tests/extractor.py:125-138 batch_create (0<->1 exchange) + utils/network.py:259-278
         if selected:
@@ -124,14 +140,16 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
                 s0, s1 = match_s[:, 0], match_s[:, 1]
                 r.quat = ctx.partII_forward(feat1[s1], feat0[s0], o1["eqv"][s1], o0["eqv"][s0], dr_s, check_range=False)
             r.trans_pre = ctx.hyp_from_quat(r.quat, dr_s, k0s, k1s)
-            res, _ = ctx.o_score(k0m, k1m, r.trans_pre, vote_order, H, inlier_dist)
+            res, vote["counts"] = ctx.o_score(k0m, k1m, r.trans_pre, vote_order, H, inlier_dist)
+            vote["order"] = vote_order
             return res.cpu().numpy()
         if ctx.supports_matched():
             r.quat = ctx.partII_forward_matched(feat0, feat1, o0["eqv"], o1["eqv"], match, r.dr_index, check_range=False)
         else:                                              # other PartII arithmetic modes take gathered rows
             r.quat = ctx.partII_forward(feat1[m1], feat0[m0], o1["eqv"][m1], o0["eqv"][m0], r.dr_index, check_range=False)
         r.trans_pre = ctx.hyp_from_quat(r.quat, r.dr_index, k0m, k1m)
-        res, _ = ctx.o_score(k0m, k1m, r.trans_pre, order_d, H, inlier_dist)      # tests/estimator.py:321-336
+        res, vote["counts"] = ctx.o_score(k0m, k1m, r.trans_pre, order_d, H, inlier_dist)      # tests/estimator.py:321-336
+        vote["order"] = order_d[:H]
         return res.cpu().numpy()                           # second host wait: the winner
 
     bh, bc = (int(v) for v in head_and_vote())
@@ -140,8 +158,25 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
         bh, bc = (int(v) for v in ctx._repeat_wider("partII", head_and_vote))
     r.best_h, r.best_count = bh, bc
     r.trans = r.trans_pre[bh if selected else int(order[bh])].cpu().numpy() if bc > 0 else np.eye(4)
+    T_start = r.trans_pre[bh if selected else int(order[bh])] if bc > 0 else None
+    if verify is not None:
+        src, tgt = (clouds[1], clouds[0]) if clouds is not None else (keys1.to(torch.float32).contiguous(), keys0.to(torch.float32).contiguous())
+        counts = vote["counts"]
+        T_ver, top, npairs, rmse, cost, info = ctx.verify_hypotheses(src, tgt, r.trans_pre, counts, int(verify), inlier_dist if verify_dist is None else verify_dist,
+                                                                     order=vote["order"], min_count=verify_min_count, distinct_tol=verify_distinct)
+        top_counts = torch.where(top >= 0, counts[top.clamp(min=0).to(torch.int64)], torch.full_like(top, -1))
+        K = int(verify)
+        host = torch.cat([T_ver.reshape(-1), top.to(torch.float64), top_counts.to(torch.float64), npairs.to(torch.float64), rmse, cost,
+                          info.to(torch.float64)]).cpu().numpy()        # the one additional host read
+        r.trans_verified = host[:12].reshape(3, 4).copy()
+        cols = [host[12 + i * K:12 + (i + 1) * K] for i in range(5)]
+        best = int(host[12 + 5 * K + 1])
+        r.verify = {"top": cols[0].astype(np.int32), "counts": cols[1].astype(np.int32), "npairs": cols[2].astype(np.int32), "rmse": cols[3].copy(),
+                    "cost": cols[4].copy(), "best": best, "fitness": float(cols[2][best]) / src.shape[0] if best >= 0 else 0.0}
+        if best >= 0:
+            T_start = T_ver
     if refine is not None and bc > 0:
-        refined(r.trans_pre[bh if selected else int(order[bh])])
+        refined(T_start)
     return r
 
 
@@ -204,7 +239,7 @@ class PairStreamer:
             r.range_repeats += 1
             return r
         r = PairResult()
-        r.match = r.dr_index = r.quat = r.trans_pre = r.order = r.hyp_rows = r.trans_refined = r.refine = None
+        r.match = r.dr_index = r.quat = r.trans_pre = r.order = r.hyp_rows = r.trans_refined = r.refine = r.trans_verified = r.verify = None
         r.eqv = (o0, o1)
         r.range_repeats = 0
         r.matches, r.best_h, r.best_count, r.trans = f["matches"], f["best_h"], f["best_count"], f["trans"]
