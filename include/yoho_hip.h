@@ -252,10 +252,15 @@ int yoho_gconv_wgrad(yoho_ctx* ctx, const float* x, const float* dy, int B, int 
 /* BatchNorm2d (train or eval statistics) + ReLU in front of a conv (utils/network.py:16-17,28-29,33-34), on (B,C,60) device tensors.
  *   yoho_bn_stats          mean (C), biased var (C) over the B x 60 values of every channel (f64 sums);
  *   yoho_bn_relu_apply     y = relu(x * scale[c] + shift[c]), scale = gamma * rsqrt(var + eps), shift = beta - mean * scale;
+ *   yoho_bn_relu_apply_sub y = relu((x - mean[c]) * scale[c] + beta[c]): the same function with the mean subtracted first, which keeps
+ *                          fp32's relative accuracy where |mean| is many standard deviations (the folded shift is rounded at the size
+ *                          of mean * scale and loses |mean| / std * 2^-24 of the output); what the training modules call;
  *   yoho_bn_relu_backward  dy -> dx, dgamma, dbeta through ReLU and the normalisation (batch_stats = 1: the statistics depend on x
  *                          as in training; 0: running statistics, the normalisation is a fixed affine map). */
 int yoho_bn_stats(yoho_ctx* ctx, const float* x, int B, int C, float* mean, float* var, void* stream);
 int yoho_bn_relu_apply(yoho_ctx* ctx, const float* x, int B, int C, const float* scale, const float* shift, float* y, void* stream);
+int yoho_bn_relu_apply_sub(yoho_ctx* ctx, const float* x, int B, int C, const float* mean, const float* scale, const float* beta, float* y,
+                           void* stream);
 int yoho_bn_relu_backward(yoho_ctx* ctx, const float* x, const float* y, const float* dy, int B, int C, const float* gamma,
                           const float* mean, const float* rstd, int batch_stats, float* dx, float* dgamma, float* dbeta, void* stream);
 

@@ -122,6 +122,7 @@ def test_every_entry_point_refuses_bad_arguments(env, hip):
         ("yoho_gconv_wgrad", (h, p(x), N, 8, 32, 32, p(eqv), N, N), EINVAL, "yoho_gconv_wgrad"),
         ("yoho_bn_stats", (h, p(x), 0, 32, p(inv), p(inv), N), EINVAL, "yoho_bn_stats"),
         ("yoho_bn_relu_apply", (h, p(x), 8, 32, N, p(inv), p(eqv), N), EINVAL, "yoho_bn_relu_apply"),
+        ("yoho_bn_relu_apply_sub", (h, p(x), 8, 32, p(inv), N, p(inv), p(eqv), N), EINVAL, "yoho_bn_relu_apply_sub"),
         ("yoho_bn_relu_backward", (h, p(x), p(x), p(x), 8, 32, p(inv), p(inv), p(inv), 1, N, p(inv), p(inv), N), EINVAL, "yoho_bn_relu_backward"),
         ("yoho_load_fcgf", (h, N, N, 0), EINVAL, "yoho_load_fcgf"),
         ("yoho_load_fcgf", (h, C.byref(cfg), C.cast(ptr_arr, C.POINTER(C.c_void_p)), 1), EINVAL, "yoho_load_fcgf"),

@@ -1255,6 +1255,14 @@ int yoho_bn_relu_apply(yoho_ctx* c, const float* x, int B, int C, const float* s
     return bn_relu_apply(x, B, C, scale, shift, y, (hipStream_t)stream);
 }
 
+int yoho_bn_relu_apply_sub(yoho_ctx* c, const float* x, int B, int C, const float* mean, const float* scale, const float* beta, float* y,
+                           void* stream) {
+    if (!c || !x || !mean || !scale || !beta || !y || B < 1 || C < 1) { set_error("yoho_bn_relu_apply_sub: bad argument"); return YOHO_EINVAL; }
+    YOHO_NEED_ALIGNED("yoho_bn_relu_apply_sub", 15, x, y);
+    HIPCHK(hipSetDevice(c->device));
+    return bn_relu_apply_sub(x, B, C, mean, scale, beta, y, (hipStream_t)stream);
+}
+
 int yoho_bn_relu_backward(yoho_ctx* c, const float* x, const float* y, const float* dy, int B, int C, const float* gamma, const float* mean,
                           const float* rstd, int batch_stats, float* dx, float* dgamma, float* dbeta, void* stream) {
     if (!c || !x || !y || !dy || !gamma || !mean || !rstd || !dx || !dgamma || !dbeta || B < 1 || C < 1) {

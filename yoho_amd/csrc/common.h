@@ -156,6 +156,7 @@ int gconv_layer(yoho_ctx* c, const float* x, int B, int cin, int cout, const flo
                 hipStream_t s);
 int bn_stats(const float* x, int B, int C, float* mean, float* var, hipStream_t s);
 int bn_relu_apply(const float* x, int B, int C, const float* scale, const float* shift, float* y, hipStream_t s);
+int bn_relu_apply_sub(const float* x, int B, int C, const float* mean, const float* scale, const float* beta, float* y, hipStream_t s);
 int bn_relu_backward(const float* x, const float* y, const float* dy, int B, int C, const float* gamma, const float* mean, const float* rstd,
                      int batch_stats, float* dx, float* dgamma, float* dbeta, hipStream_t s);
 int gconv_wgrad(yoho_ctx* c, const float* x, const float* dy, int B, int cin, int cout, float* dW, float* db, hipStream_t s);

@@ -80,8 +80,10 @@ __global__ void pad_bias_kernel(const float* __restrict__ b, int n, int npad, fl
 // table instead of a materialised (B,C,60,13) gather (utils/network.py:46-52 under autograd).  One workgroup per
 // (32 output channels, 32 input channels): thread (oi = tid >> 3, cj = tid & 7) owns dW[oi][4 cj .. 4 cj + 3][0..12] - 52 fp32
 // accumulators - and walks the batch in order (deterministic sums); per sample the two 32 x 60 blocks are staged in LDS
-// ([g][channel], so the four channels of a thread are one 16-byte read and dy is a broadcast).  Training batches are a few
-// dozen keypoints (train/trainer.py), so this kernel is judged on parity, not on the roofline.
+// ([g][channel], so the four channels of a thread are one 16-byte read and dy is a broadcast).  The sums are two-level: the 60 group
+// elements of a sample go into per-sample partial sums, the partial sums into the totals.  One fp32 chain over all B * 60 terms sat at
+// 5 (dW) to 14 (db) times the error of a blocked fp32 sum at B = 33 and grows with sqrt(B) (profiles/precision.md, "Training kernels").
+// Training batches are a few dozen keypoints (train/trainer.py), so this kernel is judged on parity, not on the roofline.
 __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dy, int B, int cin, int cout,
                                                     const int* __restrict__ nei, float* __restrict__ dW, float* __restrict__ db) {
     __shared__ float xs[G][32];
@@ -97,6 +99,12 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ x,
         for (int k = 0; k < NTAP; ++k) acc[e][k] = 0.f;
     float bsum = 0.f;
     for (int b = 0; b < B; ++b) {
+        float part[4][NTAP];                                              // this sample's share of acc, and of bsum
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int k = 0; k < NTAP; ++k) part[e][k] = 0.f;
+        float bpart = 0.f;
         __syncthreads();
         const float* xp = x + ((size_t)b * cin + cb * 32) * G;          // 32 channels x 60 group elements, contiguous
         const float* dp = dy + ((size_t)b * cout + ob * 32) * G;
@@ -108,16 +116,21 @@ __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ x,
         __syncthreads();
         for (int g = 0; g < G; ++g) {
             const float d = ds[g][oi];
-            bsum += d;
+            bpart += d;
 #pragma unroll
             for (int k = 0; k < NTAP; ++k) {
                 const float4 v = *reinterpret_cast<const float4*>(&xs[nb[g * NTAP + k]][4 * cj]);
-                acc[0][k] = fmaf(d, v.x, acc[0][k]);
-                acc[1][k] = fmaf(d, v.y, acc[1][k]);
-                acc[2][k] = fmaf(d, v.z, acc[2][k]);
-                acc[3][k] = fmaf(d, v.w, acc[3][k]);
+                part[0][k] = fmaf(d, v.x, part[0][k]);
+                part[1][k] = fmaf(d, v.y, part[1][k]);
+                part[2][k] = fmaf(d, v.z, part[2][k]);
+                part[3][k] = fmaf(d, v.w, part[3][k]);
             }
         }
+        bsum += bpart;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int k = 0; k < NTAP; ++k) acc[e][k] += part[e][k];
     }
     float* o = dW + ((size_t)(ob * 32 + oi) * cin + cb * 32 + 4 * cj) * NTAP;
 #pragma unroll
@@ -165,6 +178,18 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const float* __restr
     y[i] = fmaxf(fmaf(x[i], scale[c], shift[c]), 0.f);
 }
 
+// y = relu((x - mean[c]) * scale[c] + beta[c]): the mean leaves x before anything is rounded against it, so a channel whose mean is
+// hundreds of standard deviations keeps fp32's relative accuracy (the folded shift = beta - mean * scale above is rounded at the
+// magnitude of mean * scale: |mean| / std * 2^-24 of the output)
+__global__ __launch_bounds__(256) void bn_relu_apply_sub_kernel(const float* __restrict__ x, size_t n, int C, const float* __restrict__ mean,
+                                                                const float* __restrict__ scale, const float* __restrict__ beta,
+                                                                float* __restrict__ y) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)((i / G) % C);
+    y[i] = fmaxf(fmaf(x[i] - mean[c], scale[c], beta[c]), 0.f);
+}
+
 // backward, reductions: dz = dy where y > 0; sum_dz[c], sum_dz_xhat[c] with xhat = (x - mean) * rstd
 __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy,
                                                                  int B, int C, const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -208,6 +233,12 @@ int bn_stats(const float* x, int B, int C, float* mean, float* var, hipStream_t 
 int bn_relu_apply(const float* x, int B, int C, const float* scale, const float* shift, float* y, hipStream_t s) {
     const size_t n = (size_t)B * C * G;
     hipLaunchKernelGGL(bn_relu_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, C, scale, shift, y);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int bn_relu_apply_sub(const float* x, int B, int C, const float* mean, const float* scale, const float* beta, float* y, hipStream_t s) {
+    const size_t n = (size_t)B * C * G;
+    hipLaunchKernelGGL(bn_relu_apply_sub_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, n, C, mean, scale, beta, y);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -26,7 +26,7 @@ SYMBOLS = [
     "yoho_gconv_layer", "yoho_load_fcgf", "yoho_fcgf_voxelize", "yoho_fcgf_forward", "yoho_fcgf_forward_batch", "yoho_fcgf_voxelize_rotated", "yoho_rotate_select",
     "yoho_des2r", "yoho_des2r_indexed", "yoho_partII_forward", "yoho_partII_forward_indexed", "yoho_hyp_from_quat", "yoho_o_score", "yoho_c_ransac",
     "yoho_group_gather", "yoho_set_profiling", "yoho_get_kernel_ms", "yoho_set_gconv_mode", "yoho_set_partII_mode", "yoho_set_nn_grid",
-    "yoho_range_status", "yoho_c_ransac_device", "yoho_group_scatter", "yoho_set_nn_prefilter", "yoho_set_fcgf_sort", "yoho_fcgf_voxelize_rotated_batch", "yoho_gconv_wgrad", "yoho_bn_stats", "yoho_bn_relu_apply", "yoho_bn_relu_backward", "yoho_set_partI_schedule", "yoho_clock_probe", "yoho_group_transfer_batch",
+    "yoho_range_status", "yoho_c_ransac_device", "yoho_group_scatter", "yoho_set_nn_prefilter", "yoho_set_fcgf_sort", "yoho_fcgf_voxelize_rotated_batch", "yoho_gconv_wgrad", "yoho_bn_stats", "yoho_bn_relu_apply", "yoho_bn_relu_apply_sub", "yoho_bn_relu_backward", "yoho_set_partI_schedule", "yoho_clock_probe", "yoho_group_transfer_batch",
     "yoho_register_pair", "yoho_vote_order", "yoho_c_draw_np", "yoho_phase_profile", "yoho_phase_read", "yoho_poison_scratch",
 ]
 # the entries of include/yoho_knn.h: a header and a list of their own, because the two ABI tests pin SYMBOLS to include/yoho_hip.h
@@ -134,6 +134,7 @@ def load_library():
     lib.yoho_get_kernel_ms.argtypes = [vp, ci, C.POINTER(C.c_float)]
     lib.yoho_bn_stats.argtypes = [vp, vp, ci, ci, vp, vp, vp]
     lib.yoho_bn_relu_apply.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp]
+    lib.yoho_bn_relu_apply_sub.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp]
     lib.yoho_bn_relu_backward.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, vp]
     lib.yoho_gconv_wgrad.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp, vp]
     lib.yoho_group_scatter.argtypes = [vp, vp, ci, vp, ci, ci, vp, vp]
@@ -340,6 +341,14 @@ class Context:
         y = torch.empty_like(x)
         _check(self._lib.yoho_bn_relu_apply(self._h, _dev(x, torch.float32, "x"), x.shape[0], x.shape[1], _dev(scale, torch.float32, "scale"),
                                             _dev(shift, torch.float32, "shift"), C.c_void_p(y.data_ptr()), _stream()))
+        return y
+
+    def bn_relu_apply_sub(self, x, mean, scale, beta):
+        """y = relu((x - mean[c]) * scale[c] + beta[c]): bn_relu_apply with the mean subtracted first (accurate where |mean| >> std)"""
+        y = torch.empty_like(x)
+        _check(self._lib.yoho_bn_relu_apply_sub(self._h, _dev(x, torch.float32, "x"), x.shape[0], x.shape[1], _dev(mean, torch.float32, "mean"),
+                                                _dev(scale, torch.float32, "scale"), _dev(beta, torch.float32, "beta"),
+                                                C.c_void_p(y.data_ptr()), _stream()))
         return y
 
     def bn_relu_backward(self, x, y, dy, gamma, mean, rstd, batch_stats):

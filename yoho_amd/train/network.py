@@ -60,8 +60,8 @@ class _BNReLUFn(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, mean, var, eps, batch_stats, hctx):
         x = x.contiguous()
         rstd = torch.rsqrt(var + eps)
-        scale = (gamma * rstd).contiguous()
-        y = hctx.bn_relu_apply(x, scale, (beta - mean * scale).contiguous())
+        # subtract-first: the folded shift = beta - mean * scale of yoho_bn_relu_apply is rounded at the size of mean * scale
+        y = hctx.bn_relu_apply_sub(x, mean.contiguous(), (gamma * rstd).contiguous(), beta.detach().contiguous())
         ctx.hctx, ctx.batch_stats = hctx, batch_stats
         ctx.save_for_backward(x, y, gamma.detach().contiguous(), mean.contiguous(), rstd.contiguous())
         return y
