@@ -1,4 +1,5 @@
-"""ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h, include/yoho_refine.h, include/yoho_plane.h) + a thin tensor-level wrapper.
+"""ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h, include/yoho_refine.h, include/yoho_plane.h,
+include/yoho_verify.h, include/yoho_consist.h) + a thin tensor-level wrapper.
 
 PyTorch-ROCm tensors are the device-memory container only: every method passes
 ``tensor.data_ptr()`` and the current HIP stream to the C ABI.  There is NO CPU fallback: if the
@@ -46,6 +47,10 @@ PLANE_SYMBOLS = ["yoho_estimate_normals", "yoho_icp_plane"]
 # the entries of include/yoho_verify.h (hypotheses verified on the clouds), kept apart for the same reason
 VERIFY_SYMBOLS = ["yoho_eval_transforms", "yoho_verify_hypotheses"]
 VERIFY_MAX_K = 64                           # YOHO_VERIFY_MAX_K
+# the entries of include/yoho_consist.h (hypotheses from the match list alone), kept apart for the same reason
+CONSIST_SYMBOLS = ["yoho_consistency_graph", "yoho_sc2_scores", "yoho_consensus_hypotheses"]
+CONSIST_MAX_M = 1 << 14                     # YOHO_CONSIST_MAX_M
+CONSIST_MAX_K = 64                          # YOHO_CONSIST_MAX_K
 
 
 class ConvW(C.Structure):
@@ -91,7 +96,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -156,7 +161,10 @@ def load_library():
     lib.yoho_icp_plane.argtypes = [vp, vp, ci, vp, ci, vp, vp, C.c_float, ci, C.c_double, vp, vp, vp, vp, vp]
     lib.yoho_eval_transforms.argtypes = [vp, vp, ci, vp, ci, vp, ci, C.c_float, vp, vp, vp, vp]
     lib.yoho_verify_hypotheses.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, C.c_double, C.c_float, vp, vp, vp, vp, vp, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS:
+    lib.yoho_consistency_graph.argtypes = [vp, vp, vp, ci, C.c_double, C.c_double, vp, vp, vp]
+    lib.yoho_sc2_scores.argtypes = [vp, vp, ci, vp, vp]
+    lib.yoho_consensus_hypotheses.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -770,6 +778,51 @@ class Context:
                                                 float(max_dist), C.c_void_p(T_out.data_ptr()), C.c_void_p(top.data_ptr()), C.c_void_p(npairs.data_ptr()),
                                                 C.c_void_p(rmse.data_ptr()), C.c_void_p(cost.data_ptr()), C.c_void_p(info.data_ptr()), _stream()))
         return T_out, top, npairs, rmse, cost, info
+
+    # ---- hypotheses from the match list alone (include/yoho_consist.h) ------------------------
+    def consistency_graph(self, k0, k1, tol, min_len=0.0):
+        """k0, k1 (M,3) f64 matched keypoints, 1 <= M <= CONSIST_MAX_M -> (bits (M, W) int64, deg (M) int32), device tensors, W = (M + 63) // 64:
+        bit j % 64 of word j // 64 of row i says that matches i and j keep their distance, | |k0[i] - k0[j]| - |k1[i] - k1[j]| | < tol with
+        both lengths >= min_len (yoho_consistency_graph).  The words are the header's uint64 carried as int64: the bit pattern is the
+        contract (numpy: .view(np.uint64))."""
+        M = k0.shape[0]
+        if tuple(k0.shape) != (M, 3) or tuple(k1.shape) != (M, 3):
+            raise ValueError("consistency_graph: k0, k1 (M,3)")
+        bits = torch.empty((M, (M + 63) // 64), dtype=torch.int64, device=k0.device)
+        deg = torch.empty((M,), dtype=torch.int32, device=k0.device)
+        _check(self._lib.yoho_consistency_graph(self._h, _dev(k0, torch.float64, "k0") if M else None, _dev(k1, torch.float64, "k1") if M else None, M,
+                                                float(tol), float(min_len), C.c_void_p(bits.data_ptr()), C.c_void_p(deg.data_ptr()), _stream()))
+        return bits, deg
+
+    def sc2_scores(self, bits):
+        """bits (M, W) int64 as consistency_graph leaves it -> s2 (M) int32 on the device: per match the common compatible neighbours
+        summed over its compatible pairs (yoho_sc2_scores)."""
+        if bits.dim() != 2 or bits.shape[1] != (bits.shape[0] + 63) // 64:
+            raise ValueError("sc2_scores: bits (M, (M + 63) // 64)")
+        M = bits.shape[0]
+        s2 = torch.empty((M,), dtype=torch.int32, device=bits.device)
+        _check(self._lib.yoho_sc2_scores(self._h, _dev(bits, torch.int64, "bits") if M else None, M, C.c_void_p(s2.data_ptr()), _stream()))
+        return s2
+
+    def consensus_hypotheses(self, k0, k1, bits, s2, K):
+        """k0, k1 (M,3) f64, bits / s2 as the two methods above leave them, 1 <= K <= CONSIST_MAX_K -> (T (K,3,4) f64, seeds (K) int32,
+        sizes (K) int32, info int32[2] = (Kc, M)), device tensors: greedy seeds by s2, one per cluster, the seed's set (the matches sharing
+        at least half as many neighbours with it as its best partner) fitted by the Kabsch step (yoho_consensus_hypotheses).  A row whose
+        set has fewer than 3 members or rank below 2 is NaN with sizes = -n; rows behind Kc hold [I|0], seeds -1, sizes 0.  T chains into
+        o_score / verify_hypotheses / refit_matches without a host read."""
+        M, K = k0.shape[0], int(K)
+        if tuple(k0.shape) != (M, 3) or tuple(k1.shape) != (M, 3) or tuple(bits.shape) != (M, (M + 63) // 64) or tuple(s2.shape) != (M,):
+            raise ValueError("consensus_hypotheses: k0, k1 (M,3), bits (M, (M + 63) // 64), s2 (M)")
+        dev = k0.device
+        T = torch.empty((max(K, 0), 3, 4), dtype=torch.float64, device=dev)
+        seeds = torch.empty((max(K, 0),), dtype=torch.int32, device=dev)
+        sizes = torch.empty((max(K, 0),), dtype=torch.int32, device=dev)
+        info = torch.empty((2,), dtype=torch.int32, device=dev)
+        _check(self._lib.yoho_consensus_hypotheses(self._h, _dev(k0, torch.float64, "k0") if M else None, _dev(k1, torch.float64, "k1") if M else None, M,
+                                                   _dev(bits, torch.int64, "bits") if M else None, _dev(s2, torch.int32, "s2") if M else None, K,
+                                                   C.c_void_p(T.data_ptr()), C.c_void_p(seeds.data_ptr()), C.c_void_p(sizes.data_ptr()),
+                                                   C.c_void_p(info.data_ptr()), _stream()))
+        return T, seeds, sizes, info
 
     def mutual_nn(self, a, b):
         """a (Na,32), b (Nb,32) -> (M,2) int64 mutual nearest neighbours, ascending in a."""

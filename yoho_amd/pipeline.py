@@ -16,6 +16,7 @@ import torch
 
 class PairResult:
     __slots__ = ("match", "dr_index", "quat", "trans_pre", "best_h", "best_count", "trans", "order", "eqv", "range_repeats", "hyp_rows", "matches",
+                 "trans_consensus", "consensus",
                  "trans_refined", "refine", "trans_verified", "verify")
 
 
@@ -32,7 +33,8 @@ def describe_pair(ctx, feat0, feat1, check_range=True):
 
 def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, order_rng=None, eqv=None, estimator="yohoo", seed=0,
              hypotheses="all", refine=None, refine_iters=4, clouds=None, max_dist=None, icp_iters=30,
-             normal_radius=None, verify=None, verify_dist=None, verify_distinct=0.0, verify_min_count=1):
+             normal_radius=None, verify=None, verify_dist=None, verify_distinct=0.0, verify_min_count=1,
+             consensus=None, consensus_tol=None, consensus_min_len=0.0):
     """feat0/feat1 (K,32,60) f32 cuda (FCGF group features), keys0/keys1 (K,3) f64 cuda.
     estimator 'yohoo' (tests/evaluator.py:112-117: PartII + one-shot vote over <= max_iter per-match hypotheses, order
     shuffled by order_rng) or 'yohoc' (tests/evaluator.py:41-47: max_iter Kabsch RANSAC iterations sampled on the device
@@ -55,7 +57,14 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
     (Context.verify_hypotheses, include/yoho_verify.h).  trans, best_h and best_count stay the vote's; trans_verified (3,4) is that
     hypothesis ([I|0] when no position qualifies) and verify = dict(top, counts (of the positions in top), npairs, rmse, cost (K; -1
     behind the rows taken), best (row, -1 when none), fitness = npairs[best] / Ns), fetched in one additional host read.  With refine
-    as well the refinement starts from the verified transform, chained in on the device."""
+    as well the refinement starts from the verified transform, chained in on the device.
+    consensus: None (default) = nothing else runs, trans_consensus and consensus are None; K (1 .. hip.CONSIST_MAX_K, either estimator) =
+    beside the estimator, consensus.register_matches proposes K hypotheses from the match list alone (include/yoho_consist.h: no
+    PartII output is read) with tol = consensus_tol (None: inlier_dist), min_len = consensus_min_len, the vote at inlier_dist, clouds /
+    verify_dist / refine_iters as above; consensus is its dict, trans_consensus (3,4) its refitted transform.  Every other field stays
+    what it is without it; one additional host read.  A pair without a match gets consensus.empty_result (Kc = 0, trans_consensus = [I|0])
+    and runs nothing; one with more than hip.CONSIST_MAX_M matches is refused with a ValueError as soon as the match count is known, before
+    the estimator runs."""
     if refine not in (None, "refit", "refit+icp", "refit+icp_plane"):
         raise ValueError(f"refine must be None, 'refit', 'refit+icp' or 'refit+icp_plane', got {refine!r}")
     if verify is not None:
@@ -64,11 +73,23 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
         from .hip import VERIFY_MAX_K
         if int(verify) != verify or not 1 <= verify <= VERIFY_MAX_K:
             raise ValueError(f"verify must be None or an integer in [1, {VERIFY_MAX_K}], got {verify!r}")
+    if consensus is not None:
+        from .hip import CONSIST_MAX_K, CONSIST_MAX_M
+        if int(consensus) != consensus or not 1 <= consensus <= CONSIST_MAX_K:
+            raise ValueError(f"consensus must be None or an integer in [1, {CONSIST_MAX_K}], got {consensus!r}")
     with_icp = refine in ("refit+icp", "refit+icp_plane")
     if with_icp and (clouds is None or max_dist is None):
         raise ValueError(f"refine={refine!r} needs clouds=(cloud0, cloud1) and max_dist")
     r = PairResult()
-    r.trans_refined = r.refine = r.trans_verified = r.verify = None
+    r.trans_refined = r.refine = r.trans_verified = r.verify = r.trans_consensus = r.consensus = None
+
+    def with_consensus():
+        if consensus is not None:
+            from .consensus import register_matches
+            r.consensus = register_matches(ctx, keys0, keys1, r.match, inlier_dist if consensus_tol is None else consensus_tol, K=int(consensus),
+                                           min_len=consensus_min_len, inlier_dist=inlier_dist, refit_iters=refine_iters, clouds=clouds, max_dist=verify_dist)
+            r.trans_consensus = r.consensus["trans_refit"]
+        return r
 
     def refined(T_dev):
         # the winner's transform is still on the device: it chains into the refit without another host read in front
@@ -96,10 +117,12 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
     r.eqv = (o0, o1)
     r.match = match
     M = r.matches = match.shape[0]
+    if consensus is not None and M > CONSIST_MAX_M:         # before the estimator runs, not behind it
+        raise ValueError(f"consensus takes at most {CONSIST_MAX_M} matches, this pair has {M}")
     if M == 0:
         r.dr_index = r.quat = r.trans_pre = None
         r.best_h, r.best_count, r.trans, r.order = 0, 0, np.eye(4), None
-        return r
+        return with_consensus()
     m0, m1 = match[:, 0], match[:, 1]
     # tests/extractor.py:97-99: Batch_Des2R_torch(feats1, feats0); rows addressed in place through the match list
     r.dr_index = ctx.des2r_matched(o1["eqv"], o0["eqv"], match)
@@ -111,7 +134,7 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
         r.trans = host[:12].reshape(3, 4) if r.best_count > 0 else np.eye(4)
         if refine is not None and r.best_count > 0:
             refined(T)
-        return r
+        return with_consensus()
     if estimator != "yohoo":
         raise ValueError(f"estimator must be 'yohoo' or 'yohoc', got {estimator!r}")
     k0m, k1m = keys0[m0].contiguous(), keys1[m1].contiguous()
@@ -177,7 +200,7 @@ def run_pair(ctx, feat0, feat1, keys0, keys1, inlier_dist=0.09, max_iter=1000, o
             T_start = T_ver
     if refine is not None and bc > 0:
         refined(T_start)
-    return r
+    return with_consensus()
 
 
 class PairStreamer:
@@ -239,7 +262,7 @@ class PairStreamer:
             r.range_repeats += 1
             return r
         r = PairResult()
-        r.match = r.dr_index = r.quat = r.trans_pre = r.order = r.hyp_rows = r.trans_refined = r.refine = r.trans_verified = r.verify = None
+        r.match = r.dr_index = r.quat = r.trans_pre = r.order = r.hyp_rows = r.trans_refined = r.refine = r.trans_verified = r.verify = r.trans_consensus = r.consensus = None
         r.eqv = (o0, o1)
         r.range_repeats = 0
         r.matches, r.best_h, r.best_count, r.trans = f["matches"], f["best_h"], f["best_count"], f["trans"]
