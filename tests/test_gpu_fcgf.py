@@ -1,4 +1,4 @@
-"""FCGF backbone on the GPU (csrc/sparse.hip through the C ABI) against oracle/fcgf_oracle.py."""
+"""FCGF backbone on the GPU (csrc/sparse.hip, spmaps.hip and spconv.hip through the C ABI) against oracle/fcgf_oracle.py."""
 import hashlib
 import os
 import sys
@@ -29,6 +29,15 @@ def fctx(hip, fsd):
     c = hip.Context()
     c.load_fcgf(fsd)
     return c
+
+
+@pytest.fixture(scope="module")
+def fine_cloud():
+    """the smallest cloud here that reaches the fine-level kernels (>= 1024 row tiles = 32768 voxels at level 0: spconv16w_kernel<1> and
+    <2>, the fused heads, conv1_mfma_kernel; 42751 / 20192 / 6029 voxels at levels 0 / 1 / 2, so levels 2 and 3 run the split kernels)"""
+    coords = fo.voxelize(synth.surface_cloud(60000, seed=31, extent=3.0), 0.025)[1]
+    assert len(coords) >= 32768, len(coords)            # a change to synth must not silently take the case away
+    return torch.from_numpy(coords).cuda()
 
 
 def test_voxelize_first_occurrence(fctx):
@@ -112,11 +121,14 @@ def test_batched_clouds_equal_separate_passes(fctx):
     assert (two[0] - sep[0]).abs().max().item() < 2e-5 and torch.equal(two[0], two[1])
 
 
-def test_internal_row_orders_are_bit_identical(fctx):
+def test_internal_row_orders_are_bit_identical(fctx, fine_cloud):
     """cell-sorted level-0 rows, parity-sorted rows and skipped kernel offsets of the transposed convolutions change no bit
     of the output, and rows come back in the caller's order"""
+    n0 = fine_cloud.shape[0]
+    assert n0 >= 32768
     clouds = [torch.from_numpy(fo.voxelize(synth.surface_cloud(n, seed=sd), 0.025)[1]).cuda() for n, sd in ((6000, 5), (37, 6), (2500, 7))]
     clouds.append(torch.from_numpy(fo.voxelize(synth.surface_cloud(20000, seed=8, extent=6.0), 0.025)[1]).cuda())    # wider than the 128-voxel cell wrap
+    clouds.append(fine_cloud)                                 # the fine-level kernels
     try:
         fctx.set_fcgf_sort(False, 4)                          # hash-table coordinate maps, first-occurrence rows, no sorting at all
         ref = [fctx.fcgf_forward(c) for c in clouds] + list(fctx.fcgf_forward_batch(clouds))
@@ -130,6 +142,27 @@ def test_internal_row_orders_are_bit_identical(fctx):
     for got in outs:
         for a, b in zip(ref, got):
             assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("name,value", [("YOHO_FCGF_HEADS", "staged"), ("YOHO_FCGF_NORM", "staged"), ("YOHO_FCGF_MAPS", "full")])
+def test_staged_heads_staged_norm_and_full_maps_give_the_default_bits(hip, fsd, fctx, fine_cloud, monkeypatch, name, value):
+    """The A/B switches of the driver (read when a context is created) against the default context, on the cloud that reaches the
+    fused heads and the fused normalisation, alone and in a batch with the 37-point cloud.  common.h claims identical bits for the
+    staged heads; the duplicate-voxel test relies on the full maps; the staged normalisation sums a row's squares in the order of the
+    fused epilogues (row_normalize_kernel)."""
+    # measured at the commit before the backbone was split into three units: max abs difference 0 for all three switches, the
+    # staged normalisation included (42751-, 42751- and 37-row outputs), so all three assert equality
+    small = torch.from_numpy(fo.voxelize(synth.surface_cloud(37, seed=6), 0.025)[1]).cuda()
+    monkeypatch.setenv(name, value)
+    c = hip.Context()
+    monkeypatch.delenv(name)
+    c.load_fcgf(fsd)
+    ref = [fctx.fcgf_forward(fine_cloud)] + list(fctx.fcgf_forward_batch([fine_cloud, small]))
+    got = [c.fcgf_forward(fine_cloud)] + list(c.fcgf_forward_batch([fine_cloud, small]))
+    for a, b in zip(ref, got):
+        print("%s=%s: max abs difference %.3g over %d rows" % (name, value, (a - b).abs().max().item() if a.numel() else 0.0, a.shape[0]))
+    for a, b in zip(ref, got):
+        assert a.shape == b.shape and torch.equal(a, b)
 
 
 def test_duplicate_voxel_rows_are_computed_like_their_first_occurrence(fctx):

@@ -1,4 +1,4 @@
-"""Micro-benchmark of the FCGF backbone (csrc/sparse.hip): voxelise + forward on a synthetic surface cloud.
+"""Micro-benchmark of the FCGF backbone (csrc/sparse.hip drives csrc/spmaps.hip and csrc/spconv.hip): voxelise + forward on a synthetic surface cloud.
 usage: bench_fcgf.py [points] [reps] [rotated copies per pass]"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

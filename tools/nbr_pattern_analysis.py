@@ -2,7 +2,7 @@
 
 For the benchmarked cloud (synth.surface_cloud(300000, seed 1, extent 3 m), voxel 0.025, one rotated copy) and every level of the
 backbone: the average number of the 27 kernel offsets a row has a neighbour at, and - for several orders of the rows - the number of
-offsets that at least one row of a 128-row workgroup / 32-row wave tile reaches, i.e. the (offset, tile) steps csrc/sparse.hip's fine-level
+offsets that at least one row of a 128-row workgroup / 32-row wave tile reaches, i.e. the (offset, tile) steps csrc/spconv.hip's fine-level
 kernels cannot skip.  Orders: the rank / brick order the library uses, a global sort by the 27-bit neighbour pattern, by an 18-bit key
 (6 face + 12 edge neighbours), and the same inside segments of S consecutive brick-order rows.
 

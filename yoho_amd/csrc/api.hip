@@ -366,7 +366,6 @@ int yoho_ctx_create(int device, const float* R, const uint8_t* N, const uint8_t*
         c->env.transfer_staged = is("YOHO_TRANSFER", "staged");
         c->env.xf_steal = !is("YOHO_XF_STEAL", "0");
         c->env.nn_splits = num("YOHO_NN_SPLITS");
-        c->env.spconv_debug = num("YOHO_SPCONV_DEBUG");
         c->env.fcgf_f32 = is("YOHO_FCGF", "f32");
         c->env.fcgf_full_maps = is("YOHO_FCGF_MAPS", "full");
         c->env.fcgf_norm_staged = is("YOHO_FCGF_NORM", "staged");

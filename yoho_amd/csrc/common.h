@@ -277,7 +277,6 @@ struct yoho_env_switches {
     bool transfer_staged = false;      // YOHO_TRANSFER=staged: the feature transfer of a pass copy by copy instead of the batched grid kernels
     bool xf_steal = true;              // YOHO_XF_STEAL=0: gft16x walks its chunks by static striding instead of tickets
     int nn_splits = 0;                 // YOHO_NN_SPLITS=<n>: column splits of the matcher's Gram passes (0 = two workgroups per CU)
-    int spconv_debug = 0;              // YOHO_SPCONV_DEBUG=<bits>: ablations of the fine-level sparse conv (a -DYOHO_SPCONV_ABLATE build only)
     bool fcgf_f32 = false;             // YOHO_FCGF=f32: the backbone's weights are packed for the fp32-MFMA kernels at yoho_load_fcgf
     bool fcgf_full_maps = false;       // YOHO_FCGF_MAPS=full: every kernel map by its own probes (no mirrored / inverted maps)
     bool fcgf_norm_staged = false;     // YOHO_FCGF_NORM=staged: row normalisation as its own kernel behind the last convolution
@@ -326,7 +325,7 @@ struct yoho_ctx {
     int* d_xfctr = nullptr;      // chunk tickets of the persistent transform kernel (gft16x work stealing): [stream slot 2][launch 4][2], zero between launches
     int fcgf_cell_sort = 1;      // FCGF backbone: level-0 rows grouped by 8^3-voxel cell inside the pass (gather locality): 0 never, 1 passes of >= 2^18 rows, 2 always
     int fcgf_hash_coords = 0;    // 1: coordinate maps through hash tables even when the clouds fit rank-ordered bitmaps (YOHO_FCGF_COORDS=hash, yoho_set_fcgf_sort cell_sort | 4)
-    int fcgf_parity_sort = 1;    // transposed convolutions of the FCGF backbone walk parity-sorted rows (sparse.hip); 0: YOHO_FCGF_SORT=0
+    int fcgf_parity_sort = 1;    // transposed convolutions of the FCGF backbone walk parity-sorted rows (spmaps.hip, spconv.hip); 0: YOHO_FCGF_SORT=0
     int nn_prefilter = 1;        // mutual NN of large sets: MFMA pre-filter + exact candidates (matchf.hip); 0 = brute force (YOHO_NN=brute)
     double nn_cell = 0.0;        // > 0: 3-D nearest-neighbour searches go through a hash grid of this cell size (gridnn.hip)
     // workspace (grown on demand)

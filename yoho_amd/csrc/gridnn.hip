@@ -257,7 +257,7 @@ __global__ void gt_build_kernel(GtBatch a) {
     a.next[(size_t)b * a.mmax + i] = atomicExch(&head[s], i);
 }
 
-// the rotated keypoint as the rotate kernel (sparse.hip rotate_sel_kernel / point_of) forms it: f64 fma chain per coordinate, then float
+// the rotated keypoint as the rotate kernel (spmaps.hip rotate_sel_kernel / point_of) forms it: f64 fma chain per coordinate, then float
 __device__ __forceinline__ void gt_query_point(const GtBatch& a, int b, int k, float (&q)[3]) {
     const size_t r = (size_t)a.kidx[k];
     const double p0 = a.pts[3 * r], p1 = a.pts[3 * r + 1], p2 = a.pts[3 * r + 2];

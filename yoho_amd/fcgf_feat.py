@@ -1,4 +1,4 @@
-"""Drop-in for simple_yoho/fcgf_feat.py: the FCGF sparse-conv backbone on the HIP library (csrc/sparse.hip).
+"""Drop-in for simple_yoho/fcgf_feat.py: the FCGF sparse-conv backbone on the HIP library (csrc/sparse.hip with its kernels in csrc/spmaps.hip and csrc/spconv.hip).
 
     ext = fcgf_extractor('model/Backbone/best_val_checkpoint.pth')
     ds_points, feats = ext.run(pc, voxel_size=0.025)          # (n,3) ndarray, (n,32) cpu Tensor, unit rows

@@ -4,7 +4,7 @@
     kpts, feat_inv, feat_eqv = extractor.run(pc, voxel_size=0.025, nkpts=5000)
 
 The FCGF sparse-conv backbone (simple_yoho/fcgf_feat.py on MinkowskiEngine) is ``yoho_amd.fcgf_feat.fcgf_extractor``
-(csrc/sparse.hip), built from ``fcgf_ckpt`` as the reference does (:20); any object with ``run(pc, voxel_size) ->
+(csrc/sparse.hip, csrc/spmaps.hip, csrc/spconv.hip), built from ``fcgf_ckpt`` as the reference does (:20); any object with ``run(pc, voxel_size) ->
 (ds_points (n,3), unit-norm feats (n,32))`` can be passed as ``fcgf`` instead.  The 60-fold NN feature transfer and
 the PartI group conv run on the HIP library too.
 
