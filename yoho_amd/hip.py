@@ -1,5 +1,5 @@
 """ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h, include/yoho_refine.h, include/yoho_plane.h,
-include/yoho_verify.h, include/yoho_consist.h) + a thin tensor-level wrapper.
+include/yoho_verify.h, include/yoho_consist.h, include/yoho_keypoints.h) + a thin tensor-level wrapper.
 
 PyTorch-ROCm tensors are the device-memory container only: every method passes
 ``tensor.data_ptr()`` and the current HIP stream to the C ABI.  There is NO CPU fallback: if the
@@ -51,6 +51,12 @@ VERIFY_MAX_K = 64                           # YOHO_VERIFY_MAX_K
 CONSIST_SYMBOLS = ["yoho_consistency_graph", "yoho_sc2_scores", "yoho_consensus_hypotheses"]
 CONSIST_MAX_M = 1 << 14                     # YOHO_CONSIST_MAX_M
 CONSIST_MAX_K = 64                          # YOHO_CONSIST_MAX_K
+# the entry of include/yoho_keypoints.h (farthest-point sampling), kept apart for the same reason
+KEYPOINT_SYMBOLS = ["yoho_fps"]
+FPS_MAX_POINTS = 1 << 22                    # YOHO_FPS_MAX_POINTS
+FPS_ONE_WG_MAX = 16384                      # YOHO_FPS_ONE_WG_MAX
+FPS_BLOCK_POINTS = 1024                     # YOHO_FPS_BLOCK_POINTS
+FPS_PATHS = {"auto": 0, "one_wg": 1, "per_pick": 2}      # YOHO_FPS_AUTO, YOHO_FPS_ONE_WG, YOHO_FPS_PER_PICK
 
 
 class ConvW(C.Structure):
@@ -96,7 +102,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -164,7 +170,8 @@ def load_library():
     lib.yoho_consistency_graph.argtypes = [vp, vp, vp, ci, C.c_double, C.c_double, vp, vp, vp]
     lib.yoho_sc2_scores.argtypes = [vp, vp, ci, vp, vp]
     lib.yoho_consensus_hypotheses.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS:
+    lib.yoho_fps.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -823,6 +830,25 @@ class Context:
                                                    C.c_void_p(T.data_ptr()), C.c_void_p(seeds.data_ptr()), C.c_void_p(sizes.data_ptr()),
                                                    C.c_void_p(info.data_ptr()), _stream()))
         return T, seeds, sizes, info
+
+    # ---- keypoints (include/yoho_keypoints.h) -----------------------------------------------
+    def fps(self, pts, k, start=0, want_dist2=True, path="auto"):
+        """pts (m,3) f32, 0 <= k <= m -> (idx (k) int64, dist2 (k) f32 or None): exact farthest-point sampling from `start` in nn_search's
+        D = 3 squared arithmetic, ties to the lowest index, the k picks distinct; dist2[0] = +inf, dist2[s] the running minimum of pick s
+        when it was chosen (yoho_fps).  path "auto" / "one_wg" (m <= FPS_ONE_WG_MAX) / "per_pick": the same bytes from each."""
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError("fps: pts (m,3)")
+        if path not in FPS_PATHS:
+            raise ValueError(f"fps: path must be one of {sorted(FPS_PATHS)}, got {path!r}")
+        m, k = pts.shape[0], int(k)
+        idx = torch.empty((max(k, 0),), dtype=torch.int64, device=pts.device)
+        dist2 = torch.empty((max(k, 0),), dtype=torch.float32, device=pts.device) if want_dist2 else None
+        _dev(pts, torch.float32, "pts")
+        if k == 0:                                   # nothing to pick (an empty tensor has no address to hand to the library)
+            return idx, dist2
+        _check(self._lib.yoho_fps(self._h, _dev(pts, torch.float32, "pts"), m, k, int(start), FPS_PATHS[path], C.c_void_p(idx.data_ptr()),
+                                  C.c_void_p(dist2.data_ptr()) if want_dist2 else None, _stream()))
+        return idx, dist2
 
     def mutual_nn(self, a, b):
         """a (Na,32), b (Nb,32) -> (M,2) int64 mutual nearest neighbours, ascending in a."""

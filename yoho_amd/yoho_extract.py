@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import hip
+from . import keypoints as KP
 from . import weights as W
 from .fcgf_feat import fcgf_extractor
 from .utils import transform_points
@@ -63,9 +64,20 @@ def _to_host(*tensors):
     return tuple(outs)
 
 
+KEYPOINT_MODES = ("random", "fps")
+
+
 class yoho_extractor():
     def __init__(self, fcgf_ckpt='model/Backbone/best_val_checkpoint.pth', yoho_ckpt='model/PartI_train/model_best.pth',
-                 fcgf=None, so3_dir=None):
+                 fcgf=None, so3_dir=None, keypoints="random", keypoint_voxel=None):
+        """keypoints: "random" - the reference's np.random.permutation(len(pc))[0:nkpts] on numpy's global generator -, or "fps" -
+        farthest-point sampling on the device (yoho_amd.keypoints.select) over the first point of every voxel of
+        keypoint_voxel (None: the voxel_size of the call), from candidate 0: no draw from any generator, keypoints in pick order, a
+        smaller nkpts a prefix of a larger one."""
+        if keypoints not in KEYPOINT_MODES:
+            raise ValueError(f"yoho_extractor: keypoints must be one of {KEYPOINT_MODES}, got {keypoints!r}")
+        self.keypoints = keypoints
+        self.keypoint_voxel = keypoint_voxel
         self.ctx = hip.get_context(so3_dir=so3_dir)
         self.grs = self.ctx.tables.R64
         self.fcgf_ckpt = fcgf_ckpt
@@ -128,22 +140,41 @@ class yoho_extractor():
         np.random.permutation(len(pc))[0:nkpts] on the global generator costs 5 ms of host time for 300 k points, and nothing on the
         device depends on it until the first NN transfer - it is taken after one backbone pass per lane has been queued
         (YOHO_OVERLAP_DRAW=0: before the first pass).  It is the only draw in this method, so the generator is consumed exactly as
-        in the reference (same keypoints for the same seed)."""
+        in the reference (same keypoints for the same seed).
+        keypoints="fps": the selection is queued on lane 0 BEFORE the first pass (draw_ahead off): its one host read, the voxel count,
+        then waits for the upload alone and never for a backbone pass, and its k launches are in front of everything that needs
+        them.  The indices stay on the device (kpts = None, kidx_d): _results reads them back with the descriptors."""
+        fps = self.keypoints == "fps"
+        lanes = self.fcgf.lanes(self.lanes)
+
         def prepare(pc_d):                         # on lane 0's stream
-            kpts_index = np.random.permutation(len(pc))[0:nkpts]
-            kpts_f = torch.empty((len(kpts_index), 32, 60), dtype=torch.float32, device="cuda")
-            kidx_d = torch.from_numpy(kpts_index.astype(np.int64)).cuda()
+            if fps:
+                kidx_d = KP.select(lanes[0][0], pc_d, nkpts, voxel=voxel_size if self.keypoint_voxel is None else self.keypoint_voxel)[0]
+                kpts = None
+            else:
+                kpts_index = np.random.permutation(len(pc))[0:nkpts]
+                kidx_d = torch.from_numpy(kpts_index.astype(np.int64)).cuda()
+                kpts = pc[kpts_index]
+            kpts_f = torch.empty((kidx_d.shape[0], 32, 60), dtype=torch.float32, device="cuda")
 
             def transfer(ctx, res, g0, Rs):        # kpts_f[:, :, g0 + j] = F_j[nn(R_j keypoints, down-sampled points of copy j)]
                 ctx.group_transfer_batch(pc_d, kidx_d, list(Rs), [ds for _, _, ds in res], [f.contiguous() for _, f, _ in res], g0, kpts_f)
-            return transfer, {"kpts": pc[kpts_index], "kpts_f": kpts_f, "keep": (pc_d, kidx_d)}
+            return transfer, {"kpts": kpts, "pc": pc, "kidx_d": kidx_d, "kpts_f": kpts_f, "keep": (pc_d, kidx_d)}
 
         starts = self._pass_starts(self.grs.shape[0])
         passes = [(i0, [self.grs[i] for i in range(i0, i1)]) for i0, i1 in zip(starts[:-1], starts[1:])]
-        lanes = self.fcgf.lanes(self.lanes)
         self._side_stream = lanes[1][1] if len(lanes) > 1 else None       # the second lane's stream of the last call, for inspection
-        done, q = self.fcgf.rotated_passes(pc, passes, voxel_size, lanes, prepare, draw_ahead=self.overlap_keypoint_draw)
+        done, q = self.fcgf.rotated_passes(pc, passes, voxel_size, lanes, prepare, draw_ahead=self.overlap_keypoint_draw and not fps)
         return dict(q, done=done, main=lanes[0][1])
+
+    @staticmethod
+    def _results(q, out):
+        """(kpts, inv, eqv) of a queued fragment on the current stream, which has waited for q["done"]: the device selection's indices
+        come to the host in the same copy as the descriptors"""
+        if q["kpts"] is not None:
+            return (q["kpts"],) + _to_host(out["inv"], out["eqv"])
+        inv, eqv, kidx = _to_host(out["inv"], out["eqv"], q["kidx_d"])
+        return (q["pc"][kidx.numpy()], inv, eqv)
 
     def _extract_features_overlapped(self, pc, voxel_size, nkpts):
         q = self._queue_passes(pc, voxel_size, nkpts)
@@ -153,7 +184,7 @@ class yoho_extractor():
                 main.wait_event(e)                 # PartI reads every column of kpts_f
             self._last_group_feats = q["kpts_f"]   # (n,32,60) group features, kept for inspection
             out = self._partI(q["kpts_f"])
-            res = (q["kpts"],) + _to_host(out["inv"], out["eqv"])       # (waits for lane 0)
+            res = self._results(q, out)            # (waits for lane 0)
         if main is not cur:
             cur.wait_stream(main)                  # what the caller queues next sees a finished call, as on one stream
         return res
@@ -184,7 +215,7 @@ class yoho_extractor():
                 if tctx.partI_owner is not self:
                     tctx.load_partI(self._sd, owner=self)
                 out = tctx.partI_forward(q["kpts_f"], want_inv=True)        # (its range check waits for the tail stream only)
-                return (q["kpts"],) + _to_host(out["inv"], out["eqv"])     # (waits for the tail stream: the fragment is complete)
+                return self._results(q, out)       # (waits for the tail stream: the fragment is complete)
 
         queued = []                                # fragments queued on the lanes and not yet yielded, oldest first
 
@@ -220,7 +251,11 @@ class yoho_extractor():
         if hasattr(self.fcgf, "rotated_passes"):
             return self._extract_features_overlapped(pc, voxel_size, nkpts)
         # a backbone with run() only: the reference's host loop
-        kpts_index = np.random.permutation(len(pc))[0:nkpts]
+        if self.keypoints == "fps":
+            pc_d = torch.from_numpy(np.ascontiguousarray(np.asarray(pc, dtype=np.float64))).cuda()
+            kpts_index = KP.select(self.ctx, pc_d, nkpts, voxel=voxel_size if self.keypoint_voxel is None else self.keypoint_voxel)[0].cpu().numpy()
+        else:
+            kpts_index = np.random.permutation(len(pc))[0:nkpts]
         kpts = pc[kpts_index]
         kpts_f = torch.empty((kpts.shape[0], 32, 60), dtype=torch.float32, device="cuda")
         for i in range(self.grs.shape[0]):
