@@ -60,6 +60,20 @@ __device__ __forceinline__ void note_range_bits(int* flag, unsigned top, float l
     if (flag && top > __float_as_uint(limit)) atomicOr(flag, 1);
 }
 
+// the lanes of the wave that hold the same BITS-bit value as this one: BITS ballots; 0 for a lane that is not valid (estim.hip's
+// buckets, rfgrid.hip's digits: a lane's rank among its equals is the popcount of the result below the lane)
+template <int BITS>
+__device__ __forceinline__ unsigned long long wave_same_value(unsigned v, bool valid) {
+    unsigned long long same = __ballot(valid);
+#pragma unroll
+    for (int bit = 0; bit < BITS; ++bit) {
+        const bool on = (v >> bit) & 1u;
+        const unsigned long long bal = __ballot(on);
+        same &= on ? bal : ~bal;
+    }
+    return valid ? same : 0ull;
+}
+
 // wave-uniform slot tables of the direct-conv kernels (gconv.hip / gconv16.hip): device memory owned by the context, handed to the
 // kernels in their arguments and read there through the constant address space (scalar loads), so that contexts built on
 // different group tables can coexist in one process (round 2 kept them in __constant__ objects of the code object)

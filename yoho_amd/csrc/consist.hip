@@ -1,6 +1,6 @@
 // Geometric-consistency consensus (include/yoho_consist.h).  Compiled with -ffp-contract=off like refine.hip / verify.hip
-// (yoho_amd/build.py): the graph's distances are a stated order of rounded f64 operations, the fit is refine.hip's Kabsch step
-// (rfkabsch.h, rf_block_sum of rfgrid.h), everything between them is integer.
+// (yoho_amd/build.py): the graph's distances are a stated order of rounded f64 operations, the fit is the Kabsch step of rffit.h as
+// refine.hip's refit runs it, everything between them is integer.  rfgrid.h is here for the entries' refusals only: there is no grid.
 //
 //   cg_graph_kernel    grid (W, ceil(M / 256)): one thread per (row i, word w), the 64 partners of the word broadcast from LDS
 //   cg_deg_kernel      one wave per row: popcount of its W words
@@ -8,7 +8,7 @@
 //   cs_seed_kernel     one workgroup: K greedy rounds of vf_select_kernel's (value << 32 | ~index) maximum, neighbours of a seed killed
 //   cs_sval_kernel     grid (ceil(M / 256), K): S[seed][m] for the seed's neighbours, one wave per neighbour row, and the block's maximum
 //   cs_sum1_kernel     grid (ceil(M / 256), K): Smax, the half-of-maximum rule -> member mask, first-pass partial sums
-//   cs_mean_kernel / cs_cov_kernel / cs_solve_kernel   refine.hip's Kabsch step with a row per hypothesis
+//   cs_mean_kernel / cs_cov_kernel / cs_solve_kernel   the Kabsch step (rffit.h) with a row per hypothesis
 //
 // THE GRAPH.  Thread (i, w) computes the 64 bits C[i][64 w .. 64 w + 63] and stores one word: both triangles are computed, the
 // symmetry is IEEE's (the header), so no pass mirrors anything and no word has two writers.  The partners' six coordinates sit in LDS
@@ -34,12 +34,12 @@
 // THE HYPOTHESES.  Kc, the number of seeds, never leaves the device: K rows are launched and a workgroup whose row is >= Kc returns on
 // a loaded word (verify.hip's idiom).  S[seed][m] is recomputed for the seed's neighbours only (K deg W word operations), kept in
 // the workspace as int32 (-1 for a non-neighbour), the block maxima beside it: the kernel boundary in front of cs_sum1_kernel makes
-// Smax known to every workgroup without an atomic or a hand-off.  The member mask then drives refine.hip's two passes - centroids,
+// Smax known to every workgroup without an atomic or a hand-off.  The member mask then drives the step's two passes - centroids,
 // centred products - and one thread per row runs rf_rotation.  Every workspace byte is written before it is read.
 //
 // Registers (hipcc -O3, gfx950) and timings: profiles/consist.md; no kernel of this file uses scratch.
 #include "rfgrid.h"
-#include "rfkabsch.h"
+#include "rffit.h"
 #include "yoho_consist.h"
 #include <cmath>
 
@@ -249,33 +249,21 @@ __global__ __launch_bounds__(256) void cs_sum1_kernel(const CsState* __restrict_
         const int sv = sval[(size_t)r * M + m];
         const bool in = m == s || (sv >= 0 && 2 * sv >= smax);
         mask[(size_t)r * M + m] = in ? 1 : 0;
-        if (in) {
-            const double* a = k0 + 3 * (size_t)m;
-            const double* b = k1 + 3 * (size_t)m;
-            v[0] = 1.0; v[2] = a[0]; v[3] = a[1]; v[4] = a[2]; v[5] = b[0]; v[6] = b[1]; v[7] = b[2];
-        }
+        if (in) rf_pair_row(k0 + 3 * (size_t)m, k1 + 3 * (size_t)m, v);
     }
     rf_block_sum<8>(v, slab + ((size_t)r * nblk + blockIdx.x) * RF_SLAB);
 }
 
-// ---- the fit (refine.hip's rf_mean_kernel / rf_refit_cov_kernel / rf_solve_kernel with a row per hypothesis) -----------------------------
+// ---- the fit (the refit's rf_mean_kernel / rf_refit_cov_kernel / rf_solve_kernel of refine.hip with a row per hypothesis) -----------------
 __global__ __launch_bounds__(64) void cs_mean_kernel(const CsState* __restrict__ st, const double* __restrict__ slab, int nblk, CsRow* __restrict__ rows,
                                                      int32_t* __restrict__ sizes) {
     const int r = blockIdx.x;
     if (r >= st->Kc) return;
     __shared__ double tot[8];
-    if (threadIdx.x < 8) {
-        const double* row = slab + (size_t)r * nblk * RF_SLAB + threadIdx.x;
-        double s = 0.0;
-        for (int b = 0; b < nblk; ++b) s = __dadd_rn(s, row[(size_t)b * RF_SLAB]);
-        tot[threadIdx.x] = s;
-    }
+    rf_slab_total<8>(slab + (size_t)r * nblk * RF_SLAB, nblk, RF_SLAB, tot);
     __syncthreads();
     const int n = (int)tot[0];
-    if (threadIdx.x < 3) {
-        rows[r].c0[threadIdx.x] = n > 0 ? tot[2 + threadIdx.x] / (double)n : 0.0;
-        rows[r].c1[threadIdx.x] = n > 0 ? tot[5 + threadIdx.x] / (double)n : 0.0;
-    }
+    rf_centroids(tot, n, rows[r].c0, rows[r].c1);
     if (threadIdx.x == 0) { rows[r].n = n; rows[r].pad = 0; sizes[r] = n; }
 }
 
@@ -286,16 +274,7 @@ __global__ __launch_bounds__(256) void cs_cov_kernel(const CsState* __restrict__
     if (r >= st->Kc) return;
     const int m = blockIdx.x * 256 + threadIdx.x;
     double v[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (m < M && mask[(size_t)r * M + m]) {
-        double a[3], b[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            a[i] = __dsub_rn(k0[3 * (size_t)m + i], rows[r].c0[i]);
-            b[i] = __dsub_rn(k1[3 * (size_t)m + i], rows[r].c1[i]);
-        }
-#pragma unroll
-        for (int i = 0; i < 9; ++i) v[i] = __dmul_rn(b[i / 3], a[i % 3]);
-    }
+    if (m < M && mask[(size_t)r * M + m]) rf_centred_products(k0 + 3 * (size_t)m, k1 + 3 * (size_t)m, rows[r].c0, rows[r].c1, v);
     rf_block_sum<9>(v, slab + ((size_t)r * nblk + blockIdx.x) * RF_SLAB);
 }
 
@@ -304,12 +283,7 @@ __global__ __launch_bounds__(64) void cs_solve_kernel(const CsState* __restrict_
     const int r = blockIdx.x;
     if (r >= st->Kc) return;
     __shared__ double H[9];
-    if (threadIdx.x < 9) {
-        const double* row = slab + (size_t)r * nblk * RF_SLAB + threadIdx.x;
-        double s = 0.0;
-        for (int b = 0; b < nblk; ++b) s = __dadd_rn(s, row[(size_t)b * RF_SLAB]);
-        H[threadIdx.x] = s;
-    }
+    rf_slab_total<9>(slab + (size_t)r * nblk * RF_SLAB, nblk, RF_SLAB, H);
     __syncthreads();
     if (threadIdx.x != 0) return;
     double* T = T_out + 12 * (size_t)r;
@@ -321,17 +295,12 @@ __global__ __launch_bounds__(64) void cs_solve_kernel(const CsState* __restrict_
         sizes[r] = -cr.n;
         return;
     }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        T[4 * i] = R[3 * i]; T[4 * i + 1] = R[3 * i + 1]; T[4 * i + 2] = R[3 * i + 2];
-        T[4 * i + 3] = __dsub_rn(cr.c0[i], __dadd_rn(__dadd_rn(__dmul_rn(R[3 * i], cr.c1[0]), __dmul_rn(R[3 * i + 1], cr.c1[1])), __dmul_rn(R[3 * i + 2], cr.c1[2])));
-    }
+    rf_rigid_row(R, cr.c0, cr.c1, T);
 }
 
 static int cg_check_m(const char* fn, yoho_ctx* c, int M) {
-    if (!c || M < 1) { set_error("%s: bad argument (ctx %p, M=%d)", fn, (void*)c, M); return YOHO_EINVAL; }
-    if (M > YOHO_CONSIST_MAX_M) { set_error("%s: M=%d must not exceed YOHO_CONSIST_MAX_M = %d", fn, M, YOHO_CONSIST_MAX_M); return YOHO_EINVAL; }
-    return 0;
+    const int rc = rf_check_sizes(fn, c, "M", M, 1);
+    return rc ? rc : rf_check_limit(fn, RF_NAMED(YOHO_CONSIST_MAX_M), "M", M);
 }
 
 }  // namespace yoho
@@ -341,11 +310,12 @@ using namespace yoho;
 extern "C" {
 
 int yoho_consistency_graph(yoho_ctx* c, const double* k0, const double* k1, int M, double tol, double min_len, uint64_t* bits, int32_t* deg, void* stream) {
+    const char* fn = "yoho_consistency_graph";
     int rc;
-    if ((rc = cg_check_m("yoho_consistency_graph", c, M))) return rc;
+    if ((rc = cg_check_m(fn, c, M))) return rc;
     if (!(tol > 0.0) || !std::isfinite(tol)) { set_error("yoho_consistency_graph: tol=%g must be finite and > 0", tol); return YOHO_EINVAL; }
     if (!(min_len >= 0.0) || !std::isfinite(min_len)) { set_error("yoho_consistency_graph: min_len=%g must be finite and >= 0", min_len); return YOHO_EINVAL; }
-    if (!k0 || !k1 || !bits || !deg) { set_error("yoho_consistency_graph: bad argument (a required pointer is NULL)"); return YOHO_EINVAL; }
+    if ((rc = rf_check_pointers(fn, k0 && k1 && bits && deg))) return rc;
     YOHO_NEED_ALIGNED("yoho_consistency_graph", 7, k0, k1, bits);
     YOHO_NEED_ALIGNED("yoho_consistency_graph", 3, deg);
     HIPCHK(hipSetDevice(c->device));
@@ -358,9 +328,10 @@ int yoho_consistency_graph(yoho_ctx* c, const double* k0, const double* k1, int 
 }
 
 int yoho_sc2_scores(yoho_ctx* c, const uint64_t* bits, int M, int32_t* s2, void* stream) {
+    const char* fn = "yoho_sc2_scores";
     int rc;
-    if ((rc = cg_check_m("yoho_sc2_scores", c, M))) return rc;
-    if (!bits || !s2) { set_error("yoho_sc2_scores: bad argument (a required pointer is NULL)"); return YOHO_EINVAL; }
+    if ((rc = cg_check_m(fn, c, M)) ||
+        (rc = rf_check_pointers(fn, bits && s2))) return rc;
     YOHO_NEED_ALIGNED("yoho_sc2_scores", 7, bits);
     YOHO_NEED_ALIGNED("yoho_sc2_scores", 3, s2);
     HIPCHK(hipSetDevice(c->device));
@@ -380,10 +351,11 @@ int yoho_sc2_scores(yoho_ctx* c, const uint64_t* bits, int M, int32_t* s2, void*
 
 int yoho_consensus_hypotheses(yoho_ctx* c, const double* k0, const double* k1, int M, const uint64_t* bits, const int32_t* s2, int K, double* T_out,
                               int32_t* seeds, int32_t* sizes, int32_t* info, void* stream) {
+    const char* fn = "yoho_consensus_hypotheses";
     int rc;
-    if ((rc = cg_check_m("yoho_consensus_hypotheses", c, M))) return rc;
-    if (K < 1 || K > YOHO_CONSIST_MAX_K) { set_error("yoho_consensus_hypotheses: K=%d must be in [1, YOHO_CONSIST_MAX_K = %d]", K, YOHO_CONSIST_MAX_K); return YOHO_EINVAL; }
-    if (!k0 || !k1 || !bits || !s2 || !T_out || !seeds || !sizes || !info) { set_error("yoho_consensus_hypotheses: bad argument (a required pointer is NULL)"); return YOHO_EINVAL; }
+    if ((rc = cg_check_m(fn, c, M)) ||
+        (rc = rf_check_range(fn, "K", K, 1, RF_NAMED(YOHO_CONSIST_MAX_K))) ||
+        (rc = rf_check_pointers(fn, k0 && k1 && bits && s2 && T_out && seeds && sizes && info))) return rc;
     YOHO_NEED_ALIGNED("yoho_consensus_hypotheses", 7, k0, k1, bits, T_out);
     YOHO_NEED_ALIGNED("yoho_consensus_hypotheses", 3, s2, seeds, sizes, info);
     HIPCHK(hipSetDevice(c->device));

@@ -320,17 +320,6 @@ __global__ __launch_bounds__(256) void cprep_kernel(const int64_t* __restrict__ 
 // the order of the reference's R_index_pre_statistic lists (tests/estimator.py:34-51).
 constexpr int CS_WAVES = 16;
 
-__device__ __forceinline__ unsigned long long same_bucket_lanes(int b, bool valid) {
-    unsigned long long same = __ballot(valid);
-#pragma unroll
-    for (int bit = 0; bit < 6; ++bit) {
-        const bool on = (b >> bit) & 1;
-        const unsigned long long bal = __ballot(on);
-        same &= on ? bal : ~bal;
-    }
-    return valid ? same : 0ull;
-}
-
 __global__ __launch_bounds__(64 * CS_WAVES) void cstat_kernel(const unsigned char* __restrict__ dr8, int M, CStat* __restrict__ st, int* __restrict__ members) {
     __shared__ volatile int wcnt[CS_WAVES][64];      // pass 1: counts of wave w; pass 2: its cursors
     __shared__ int tot[G];
@@ -344,7 +333,7 @@ __global__ __launch_bounds__(64 * CS_WAVES) void cstat_kernel(const unsigned cha
         const int m = base + lane;
         const bool valid = m < m1;
         const int b = valid ? dr8[m] : 0;
-        const unsigned long long same = same_bucket_lanes(b, valid);
+        const unsigned long long same = wave_same_value<6>((unsigned)b, valid);
         if (valid && (same & below) == 0ull) wcnt[w][b] += __popcll(same);       // one writer per bucket and wave
         __builtin_amdgcn_wave_barrier();
     }
@@ -384,7 +373,7 @@ __global__ __launch_bounds__(64 * CS_WAVES) void cstat_kernel(const unsigned cha
         const int m = base + lane;
         const bool valid = m < m1;
         const int b = valid ? dr8[m] : 0;
-        const unsigned long long same = same_bucket_lanes(b, valid);
+        const unsigned long long same = wave_same_value<6>((unsigned)b, valid);
         int cur = 0;
         if (valid) cur = wcnt[w][b];
         __builtin_amdgcn_wave_barrier();

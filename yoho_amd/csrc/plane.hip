@@ -1,6 +1,6 @@
-// Surface normals and point-to-plane ICP (include/yoho_plane.h).  Compiled with -ffp-contract=off like refine.hip (yoho_amd/build.py),
-// whose cell-sorted grid, walk and fixed-order f64 sums it shares through rfgrid.h: THE GRID, THE QUERY's exactness argument and THE SUMS
-// are described in refine.hip and carry over unchanged.
+// Surface normals and point-to-plane ICP (include/yoho_plane.h).  Compiled with -ffp-contract=off like refine.hip (yoho_amd/build.py).
+// The cell-sorted grid and its walk come from rfgrid.hip / rfgrid.h (THE GRID, THE QUERY's exactness argument), the fixed-order f64
+// sums and the rounded transform from rffit.h (THE SUMS, rf_apply); both carry over unchanged.
 //
 //   pl_normals_kernel      yoho_estimate_normals: one lane per point over the 27 cells around it, ten accumulators, a 3 x 3 Jacobi
 //   pl_pair_kernel         ICP: transform + rf_walk + the normal test + first-pass partial sums {n, SUM x}
@@ -9,7 +9,7 @@
 //   pl_solve_kernel        one wave: rmse, the 6 x 6 Cholesky solve, exp([w]x), the update and the stop word
 //
 // THE NORMALS.  The grid is built over the points themselves with cell side radius (1 + 2^-10), so the 27 cells around a point hold
-// every j with d2 < gate2 (refine.hip (1) - (3), with the point as the query).  A count needs more than the nearest-neighbour walk
+// every j with d2 < gate2 (rfgrid.hip (1) - (3), with the point as the query).  A count needs more than the nearest-neighbour walk
 // does: there a point met twice changes nothing, here it would be counted twice.  Two of the 27 cells can share a bucket - clamped
 // neighbour cells are the same cell, and different cells can hash to one slot - so the 27 slots are computed first and a slot equal
 // to an earlier one is skipped: every bucket is walked once, every point of it goes through the exact f32 test, and count is exact.
@@ -25,6 +25,7 @@
 //
 // Registers (hipcc -O3, gfx950) are recorded in profiles/plane_icp.md; no kernel of this file uses scratch.
 #include "rfgrid.h"
+#include "rffit.h"
 #include "yoho_plane.h"
 #include <cmath>
 
@@ -150,14 +151,6 @@ __global__ void pl_init_kernel(PlState* __restrict__ st, const double* __restric
     for (int k = t; k < iters; k += blockDim.x) { ints[k] = -1; dbls[k] = -1.0; }
 }
 
-// x = ((r0 sx + r1 sy) + r2 sz) + t per coordinate, every operation rounded
-__device__ __forceinline__ void pl_transform(const double* __restrict__ T, const float* __restrict__ src, int e, double (&x)[3]) {
-    const double s0 = (double)src[3 * (size_t)e], s1 = (double)src[3 * (size_t)e + 1], s2 = (double)src[3 * (size_t)e + 2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-        x[i] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T[4 * i], s0), __dmul_rn(T[4 * i + 1], s1)), __dmul_rn(T[4 * i + 2], s2)), T[4 * i + 3]);
-}
-
 // first pass: pair[e] = partner of source point e when the pair is kept (else -1), slab row = {n, SUM x (3)} of the block
 __global__ __launch_bounds__(256) void pl_pair_kernel(const PlState* __restrict__ st, RfGrid g, const float* __restrict__ src, int Ns,
                                                       const float* __restrict__ nrm, int* __restrict__ pair, double* __restrict__ slab) {
@@ -166,7 +159,7 @@ __global__ __launch_bounds__(256) void pl_pair_kernel(const PlState* __restrict_
     double v[4] = {0.0, 0.0, 0.0, 0.0};
     if (e < Ns) {
         double x[3];
-        pl_transform(st->T, src, e, x);
+        rf_apply(st->T, src, e, x);
         const float q[3] = {(float)x[0], (float)x[1], (float)x[2]};
         float bd;
         int bi;
@@ -187,11 +180,7 @@ __global__ __launch_bounds__(256) void pl_pair_kernel(const PlState* __restrict_
 __global__ __launch_bounds__(64) void pl_mean_kernel(PlState* __restrict__ st, const double* __restrict__ slab, int nblk, int it, int32_t* __restrict__ npairs) {
     if (st->stop) return;
     __shared__ double tot[4];
-    if (threadIdx.x < 4) {
-        double s = 0.0;
-        for (int b = 0; b < nblk; ++b) s = __dadd_rn(s, slab[(size_t)b * PL_SLAB + threadIdx.x]);
-        tot[threadIdx.x] = s;
-    }
+    rf_slab_total<4>(slab, nblk, PL_SLAB, tot);
     __syncthreads();
     const int n = (int)tot[0];
     if (threadIdx.x < 3) st->c[threadIdx.x] = n > 0 ? tot[1 + threadIdx.x] / (double)n : 0.0;
@@ -209,7 +198,7 @@ __global__ __launch_bounds__(256) void pl_normeq_kernel(const PlState* __restric
     const int j = e < Ns ? pair[e] : -1;
     if (j >= 0) {
         double x[3], J[6];
-        pl_transform(st->T, src, e, x);
+        rf_apply(st->T, src, e, x);
         const double ux = __dsub_rn(x[0], st->c[0]), uy = __dsub_rn(x[1], st->c[1]), uz = __dsub_rn(x[2], st->c[2]);
         const double nx = (double)nrm[3 * (size_t)j], ny = (double)nrm[3 * (size_t)j + 1], nz = (double)nrm[3 * (size_t)j + 2];
         const double r = __dadd_rn(__dadd_rn(__dmul_rn(nx, __dsub_rn(x[0], (double)tgt[3 * (size_t)j])), __dmul_rn(ny, __dsub_rn(x[1], (double)tgt[3 * (size_t)j + 1]))),
@@ -299,11 +288,7 @@ __global__ __launch_bounds__(64) void pl_solve_kernel(PlState* __restrict__ st, 
                                                       double* __restrict__ rmse) {
     if (st->stop) return;
     __shared__ double S[PL_NSUM];
-    if (threadIdx.x < PL_NSUM) {
-        double s = 0.0;
-        for (int b = 0; b < nblk; ++b) s = __dadd_rn(s, slab[(size_t)b * PL_SLAB + threadIdx.x]);
-        S[threadIdx.x] = s;
-    }
+    rf_slab_total<PL_NSUM>(slab, nblk, PL_SLAB, S);
     __syncthreads();
     if (threadIdx.x != 0) return;
     const int n = st->n;
@@ -341,19 +326,19 @@ extern "C" {
 
 int yoho_estimate_normals(yoho_ctx* c, const float* pts, int N, float radius, int min_nbrs, float vx, float vy, float vz, float* normals, int32_t* count,
                           float* curv, void* stream) {
-    if (!c || N < 1) { set_error("yoho_estimate_normals: bad argument (ctx %p, N=%d)", (void*)c, N); return YOHO_EINVAL; }
-    if (N > YOHO_REFINE_MAX_POINTS) { set_error("yoho_estimate_normals: N=%d must not exceed YOHO_REFINE_MAX_POINTS = %d", N, YOHO_REFINE_MAX_POINTS); return YOHO_EINVAL; }
-    if (rf_bad_radius(radius)) { set_error("yoho_estimate_normals: radius=%g must be finite and > 0", (double)radius); return YOHO_EINVAL; }
+    const char* fn = "yoho_estimate_normals";
+    int rc;
+    if ((rc = rf_check_sizes(fn, c, "N", N, 1)) || (rc = rf_check_limit(fn, RF_NAMED(YOHO_REFINE_MAX_POINTS), "N", N)) ||
+        (rc = rf_check_radius(fn, "radius", radius))) return rc;
     if (min_nbrs < 3) { set_error("yoho_estimate_normals: min_nbrs=%d must be at least 3", min_nbrs); return YOHO_EINVAL; }
     if (!std::isfinite(vx) || !std::isfinite(vy) || !std::isfinite(vz)) {
         set_error("yoho_estimate_normals: viewpoint (%g, %g, %g) must be finite", (double)vx, (double)vy, (double)vz);
         return YOHO_EINVAL;
     }
-    if (!pts || !normals || !count) { set_error("yoho_estimate_normals: bad argument (a required pointer is NULL)"); return YOHO_EINVAL; }
+    if ((rc = rf_check_pointers(fn, pts && normals && count))) return rc;
     YOHO_NEED_ALIGNED("yoho_estimate_normals", 3, pts, normals, count, curv);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    int rc;
     RfGridWs w;
     if ((rc = bind_ws(c, s, [&](Arena& ar) { rf_grid_layout(ar, N, w); }))) return rc;
     RfGrid g;
@@ -365,24 +350,15 @@ int yoho_estimate_normals(yoho_ctx* c, const float* pts, int N, float radius, in
 
 int yoho_icp_plane(yoho_ctx* c, const float* src, int Ns, const float* tgt, int Nt, const float* tgt_normals, const double* T_in, float max_dist, int iters,
                    double tol, double* T_out, int32_t* npairs, double* rmse, int32_t* info, void* stream) {
-    if (!c || Ns < 1 || Nt < 1) { set_error("yoho_icp_plane: bad argument (ctx %p, Ns=%d, Nt=%d)", (void*)c, Ns, Nt); return YOHO_EINVAL; }
-    if (Ns > YOHO_REFINE_MAX_POINTS || Nt > YOHO_REFINE_MAX_POINTS) {
-        set_error("yoho_icp_plane: Ns=%d, Nt=%d must not exceed YOHO_REFINE_MAX_POINTS = %d", Ns, Nt, YOHO_REFINE_MAX_POINTS);
-        return YOHO_EINVAL;
-    }
-    if (iters < 0 || iters > YOHO_ICP_MAX_ITERS) { set_error("yoho_icp_plane: iters=%d must be in [0, YOHO_ICP_MAX_ITERS = %d]", iters, YOHO_ICP_MAX_ITERS); return YOHO_EINVAL; }
-    if (rf_bad_radius(max_dist)) { set_error("yoho_icp_plane: max_dist=%g must be finite and > 0", (double)max_dist); return YOHO_EINVAL; }
-    if (std::isnan(tol)) { set_error("yoho_icp_plane: tol is NaN"); return YOHO_EINVAL; }
-    if (!src || !tgt || !tgt_normals || !T_in || !T_out || !info || (iters > 0 && (!npairs || !rmse))) {
-        set_error("yoho_icp_plane: bad argument (a required pointer is NULL)");
-        return YOHO_EINVAL;
-    }
+    const char* fn = "yoho_icp_plane";
+    int rc;
+    if ((rc = rf_check_icp(fn, c, Ns, Nt, iters, max_dist, tol)) ||
+        (rc = rf_check_pointers(fn, src && tgt && tgt_normals && T_in && T_out && info && (iters == 0 || (npairs && rmse))))) return rc;
     YOHO_NEED_ALIGNED("yoho_icp_plane", 3, src, tgt, tgt_normals, npairs, info);
     YOHO_NEED_ALIGNED("yoho_icp_plane", 7, T_in, T_out, rmse);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int nblk = (Ns + 255) / 256;
-    int rc;
     PlState* st = nullptr;
     double* slab = nullptr;
     int* pair = nullptr;

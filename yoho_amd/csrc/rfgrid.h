@@ -1,10 +1,11 @@
-// The cell-sorted grid and the fixed-order f64 block sum of refine.hip, shared with plane.hip: the device-side pieces (rf_cell /
-// rf_slot, RfGrid, rf_walk, rf_block_sum) are inline here, the grid build (rf_grid_layout / rf_build_grid and its kernels) stays in
-// refine.hip, where THE GRID, THE QUERY and THE SUMS are described, and is declared below.  Include from translation units compiled
+// The cell-sorted grid over a target cloud, as its users see it: the device-side pieces of a query (rf_cell / rf_slot, RfGrid, rf_walk)
+// inline, the workspace and the two host calls that build it (rfgrid.hip, where THE GRID and THE QUERY are described), and the
+// refusals the entries of the family share.  The sums and the Kabsch step are in rffit.h.  Include from translation units compiled
 // with -ffp-contract=off only.
 #pragma once
 #include "common.h"
 #include "nnmath.h"
+#include "yoho_refine.h"
 #include <cmath>
 
 namespace yoho {
@@ -52,26 +53,6 @@ __device__ __forceinline__ void rf_walk(const RfGrid& g, const float (&q)[3], fl
     }
 }
 
-// ---- the sums ------------------------------------------------------------------------------------------------------------------
-template <int NV>
-__device__ __forceinline__ void rf_block_sum(double (&v)[NV], double* __restrict__ slab_row) {
-    __shared__ double red[4][NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v[k] = __dadd_rn(v[k], __shfl_xor(v[k], o));
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < NV; ++k) red[threadIdx.x >> 6][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        const int k = threadIdx.x;
-        slab_row[k] = __dadd_rn(__dadd_rn(__dadd_rn(red[0][k], red[1][k]), red[2][k]), red[3][k]);
-    }
-}
-
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 struct RfGridWs {
     unsigned nslots; int bits, nblk;
@@ -79,9 +60,45 @@ struct RfGridWs {
     int* hist; int* start; float4* pk;
 };
 
-// the grid's buffers as one run of takes inside the caller's arena layout; the build queues the sort on `s` (refine.hip)
+// the grid's buffers as one run of takes inside the caller's arena layout; the build queues the sort on `s` (rfgrid.hip)
 void rf_grid_layout(Arena& ar, int Nt, RfGridWs& w);
 int rf_build_grid(const float* tgt, int Nt, float max_dist, const RfGridWs& w, RfGrid& g, hipStream_t s);
 inline bool rf_bad_radius(float r) { return !(r > 0.f) || !std::isfinite(r); }
+
+// ---- the refusals the entries share: 0, or YOHO_EINVAL with the error set -----------------------------------------------------------
+#define RF_NAMED(limit) #limit, limit          // a limit of the public headers with its name, for the message
+#define RF_REFUSE(...) (set_error(__VA_ARGS__), YOHO_EINVAL)
+// the context and one or two sizes (nb == nullptr: one) against their smallest values
+inline int rf_check_sizes(const char* fn, const void* c, const char* na, int a, int amin, const char* nb = nullptr, int b = 0, int bmin = 0) {
+    if (c && a >= amin && (!nb || b >= bmin)) return 0;
+    return nb ? RF_REFUSE("%s: bad argument (ctx %p, %s=%d, %s=%d)", fn, c, na, a, nb, b) : RF_REFUSE("%s: bad argument (ctx %p, %s=%d)", fn, c, na, a);
+}
+// one or two sizes against a named limit
+inline int rf_check_limit(const char* fn, const char* limit_name, int limit, const char* na, int a, const char* nb = nullptr, int b = 0) {
+    if (a <= limit && (!nb || b <= limit)) return 0;
+    return nb ? RF_REFUSE("%s: %s=%d, %s=%d must not exceed %s = %d", fn, na, a, nb, b, limit_name, limit)
+              : RF_REFUSE("%s: %s=%d must not exceed %s = %d", fn, na, a, limit_name, limit);
+}
+// a count (iters, K, H) in [lo, a named maximum]
+inline int rf_check_range(const char* fn, const char* name, int v, int lo, const char* max_name, int hi) {
+    return v >= lo && v <= hi ? 0 : RF_REFUSE("%s: %s=%d must be in [%d, %s = %d]", fn, name, v, lo, max_name, hi);
+}
+inline int rf_check_radius(const char* fn, const char* name, float r) {
+    return rf_bad_radius(r) ? RF_REFUSE("%s: %s=%g must be finite and > 0", fn, name, (double)r) : 0;
+}
+inline int rf_check_tol(const char* fn, double tol) { return std::isnan(tol) ? RF_REFUSE("%s: tol is NaN", fn) : 0; }
+inline int rf_check_pointers(const char* fn, bool all_there) { return all_there ? 0 : RF_REFUSE("%s: bad argument (a required pointer is NULL)", fn); }
+// a source and a target cloud of at least one point each
+inline int rf_check_clouds(const char* fn, const void* c, int Ns, int Nt) {
+    const int rc = rf_check_sizes(fn, c, "Ns", Ns, 1, "Nt", Nt, 1);
+    return rc ? rc : rf_check_limit(fn, RF_NAMED(YOHO_REFINE_MAX_POINTS), "Ns", Ns, "Nt", Nt);
+}
+// what yoho_icp_refine and yoho_icp_plane refuse before they look at their pointers, in that order
+inline int rf_check_icp(const char* fn, const void* c, int Ns, int Nt, int iters, float max_dist, double tol) {
+    int rc;
+    if ((rc = rf_check_clouds(fn, c, Ns, Nt)) || (rc = rf_check_range(fn, "iters", iters, 0, RF_NAMED(YOHO_ICP_MAX_ITERS))) ||
+        (rc = rf_check_radius(fn, "max_dist", max_dist))) return rc;
+    return rf_check_tol(fn, tol);
+}
 
 }  // namespace yoho

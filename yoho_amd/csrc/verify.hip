@@ -1,6 +1,6 @@
 // Verification of hypotheses on the clouds (include/yoho_verify.h).  Compiled with -ffp-contract=off like refine.hip
-// (yoho_amd/build.py), whose cell-sorted grid, walk and fixed-order f64 sums it shares through rfgrid.h: THE GRID, THE QUERY's exactness
-// argument and THE SUMS are described in refine.hip and carry over unchanged.
+// (yoho_amd/build.py).  The cell-sorted grid and its walk come from rfgrid.hip / rfgrid.h (THE GRID, THE QUERY's exactness argument),
+// the fixed-order f64 sums and the rounded transform from rffit.h (THE SUMS, rf_apply); both carry over unchanged.
 //
 //   vf_select_kernel   one workgroup: the best K distinct positions of a vote (greedy, with suppression), their rows gathered
 //   vf_eval_kernel     grid (ceil(Ns / 256), K), one lane per (source point, row): transform + rf_walk + the three partial sums
@@ -17,16 +17,17 @@
 // share one evaluation kernel.
 //
 // THE EVALUATION.  blockIdx.y is the row: its 12 doubles are the same for the whole workgroup and reach the lanes through scalar
-// loads.  Each lane transforms its source point with rf_icp_pair_kernel's expression (refine.hip), walks the 27 cells, and
+// loads.  Each lane transforms its source point with rf_icp_pair_kernel's expression (rf_apply), walks the 27 cells, and
 // contributes {1, d2, d2} when it has a partner and {0, +0.0, gate2} when not; rf_block_sum writes the block's three sums to the slab
 // row of (row, block).  No float atomics, no grid-wide barrier: vf_sum_kernel adds a row's slabs in block order, one thread per
-// component, as rf_mean_kernel does - serial, nblk dependent additions, which is the price of the stated order.  Kc, the number of
+// component (rf_slab_total) - serial, nblk dependent additions, which is the price of the stated order.  Kc, the number of
 // rows selected, never leaves the device: K rows are launched and a workgroup whose row is >= Kc returns on a loaded word, which is
 // wave-uniform (yoho_icp_refine's idiom for the iterations behind a stop).  Every workspace byte is written (vf_select_kernel, the
 // grid build, the evaluation) before it is read.
 //
 // Registers (hipcc -O3, gfx950) and timings are recorded in profiles/verify.md; no kernel of this file uses scratch.
 #include "rfgrid.h"
+#include "rffit.h"
 #include "yoho_verify.h"
 #include <cmath>
 
@@ -100,11 +101,9 @@ __global__ __launch_bounds__(256) void vf_eval_kernel(const VfState* __restrict_
     const int e = blockIdx.x * 256 + threadIdx.x;
     double v[3] = {0.0, 0.0, 0.0};
     if (e < Ns) {
-        const double s0 = (double)src[3 * (size_t)e], s1 = (double)src[3 * (size_t)e + 1], s2 = (double)src[3 * (size_t)e + 2];
-        float q[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            q[i] = (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(T[4 * i], s0), __dmul_rn(T[4 * i + 1], s1)), __dmul_rn(T[4 * i + 2], s2)), T[4 * i + 3]);
+        double x[3];
+        rf_apply(T, src, e, x);
+        const float q[3] = {(float)x[0], (float)x[1], (float)x[2]};
         float bd;
         int bi;
         rf_walk(g, q, bd, bi);
@@ -122,12 +121,7 @@ __global__ __launch_bounds__(64) void vf_sum_kernel(const VfState* __restrict__ 
     const int k = blockIdx.x;
     if (st && k >= st->Kc) return;
     __shared__ double tot[3];
-    if (threadIdx.x < 3) {
-        const double* row = slab + (size_t)k * nblk * VF_SLAB + threadIdx.x;
-        double s = 0.0;
-        for (int b = 0; b < nblk; ++b) s = __dadd_rn(s, row[(size_t)b * VF_SLAB]);
-        tot[threadIdx.x] = s;
-    }
+    rf_slab_total<3>(slab + (size_t)k * nblk * VF_SLAB, nblk, VF_SLAB, tot);
     __syncthreads();
     if (threadIdx.x == 0) {
         const int n = (int)tot[0];
@@ -161,18 +155,6 @@ __global__ __launch_bounds__(64) void vf_pick_kernel(const VfState* __restrict__
     if (t < 12) T_out[t] = best >= 0 ? Tsel[12 * (size_t)best + t] : (t % 5 == 0 ? 1.0 : 0.0);       // [I | 0] without a hypothesis
 }
 
-// the arguments the two entries share; 0 or YOHO_EINVAL with the error set
-static int vf_check_clouds(const char* fn, yoho_ctx* c, int Ns, int Nt, int K, float max_dist) {
-    if (!c || Ns < 1 || Nt < 1) { set_error("%s: bad argument (ctx %p, Ns=%d, Nt=%d)", fn, (void*)c, Ns, Nt); return YOHO_EINVAL; }
-    if (Ns > YOHO_REFINE_MAX_POINTS || Nt > YOHO_REFINE_MAX_POINTS) {
-        set_error("%s: Ns=%d, Nt=%d must not exceed YOHO_REFINE_MAX_POINTS = %d", fn, Ns, Nt, YOHO_REFINE_MAX_POINTS);
-        return YOHO_EINVAL;
-    }
-    if (K < 1 || K > YOHO_VERIFY_MAX_K) { set_error("%s: K=%d must be in [1, YOHO_VERIFY_MAX_K = %d]", fn, K, YOHO_VERIFY_MAX_K); return YOHO_EINVAL; }
-    if (rf_bad_radius(max_dist)) { set_error("%s: max_dist=%g must be finite and > 0", fn, (double)max_dist); return YOHO_EINVAL; }
-    return 0;
-}
-
 }  // namespace yoho
 
 using namespace yoho;
@@ -181,9 +163,10 @@ extern "C" {
 
 int yoho_eval_transforms(yoho_ctx* c, const float* src, int Ns, const float* tgt, int Nt, const double* T, int K, float max_dist, int32_t* npairs,
                          double* rmse, double* cost, void* stream) {
+    const char* fn = "yoho_eval_transforms";
     int rc;
-    if ((rc = vf_check_clouds("yoho_eval_transforms", c, Ns, Nt, K, max_dist))) return rc;
-    if (!src || !tgt || !T || !npairs || !rmse || !cost) { set_error("yoho_eval_transforms: bad argument (a required pointer is NULL)"); return YOHO_EINVAL; }
+    if ((rc = rf_check_clouds(fn, c, Ns, Nt)) || (rc = rf_check_range(fn, "K", K, 1, RF_NAMED(YOHO_VERIFY_MAX_K))) ||
+        (rc = rf_check_radius(fn, "max_dist", max_dist)) || (rc = rf_check_pointers(fn, src && tgt && T && npairs && rmse && cost))) return rc;
     YOHO_NEED_ALIGNED("yoho_eval_transforms", 3, src, tgt, npairs);
     YOHO_NEED_ALIGNED("yoho_eval_transforms", 7, T, rmse, cost);
     HIPCHK(hipSetDevice(c->device));
@@ -206,15 +189,13 @@ int yoho_eval_transforms(yoho_ctx* c, const float* src, int Ns, const float* tgt
 int yoho_verify_hypotheses(yoho_ctx* c, const float* src, int Ns, const float* tgt, int Nt, const double* T, const int64_t* order, const int32_t* counts,
                            int H, int K, int min_count, double distinct_tol, float max_dist, double* T_out, int32_t* top, int32_t* npairs, double* rmse,
                            double* cost, int32_t* info, void* stream) {
+    const char* fn = "yoho_verify_hypotheses";
     int rc;
-    if ((rc = vf_check_clouds("yoho_verify_hypotheses", c, Ns, Nt, K, max_dist))) return rc;
-    if (H < 0 || H > YOHO_REFINE_MAX_POINTS) { set_error("yoho_verify_hypotheses: H=%d must be in [0, YOHO_REFINE_MAX_POINTS = %d]", H, YOHO_REFINE_MAX_POINTS); return YOHO_EINVAL; }
+    if ((rc = rf_check_clouds(fn, c, Ns, Nt)) || (rc = rf_check_range(fn, "K", K, 1, RF_NAMED(YOHO_VERIFY_MAX_K))) ||
+        (rc = rf_check_radius(fn, "max_dist", max_dist)) || (rc = rf_check_range(fn, "H", H, 0, RF_NAMED(YOHO_REFINE_MAX_POINTS)))) return rc;
     if (min_count < 1) { set_error("yoho_verify_hypotheses: min_count=%d must be at least 1", min_count); return YOHO_EINVAL; }
     if (!(distinct_tol >= 0.0) || !std::isfinite(distinct_tol)) { set_error("yoho_verify_hypotheses: distinct_tol=%g must be finite and >= 0", distinct_tol); return YOHO_EINVAL; }
-    if (!src || !tgt || !T_out || !top || !npairs || !rmse || !cost || !info || (H > 0 && (!T || !counts))) {
-        set_error("yoho_verify_hypotheses: bad argument (a required pointer is NULL)");
-        return YOHO_EINVAL;
-    }
+    if ((rc = rf_check_pointers(fn, src && tgt && T_out && top && npairs && rmse && cost && info && (H == 0 || (T && counts))))) return rc;
     YOHO_NEED_ALIGNED("yoho_verify_hypotheses", 3, src, tgt, counts, top, npairs, info);
     YOHO_NEED_ALIGNED("yoho_verify_hypotheses", 7, T, order, T_out, rmse, cost);
     HIPCHK(hipSetDevice(c->device));
