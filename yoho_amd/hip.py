@@ -1,5 +1,5 @@
 """ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h, include/yoho_refine.h, include/yoho_plane.h,
-include/yoho_verify.h, include/yoho_consist.h, include/yoho_keypoints.h) + a thin tensor-level wrapper.
+include/yoho_verify.h, include/yoho_consist.h, include/yoho_keypoints.h, include/yoho_multiway.h) + a thin tensor-level wrapper.
 
 PyTorch-ROCm tensors are the device-memory container only: every method passes
 ``tensor.data_ptr()`` and the current HIP stream to the C ABI.  There is NO CPU fallback: if the
@@ -57,6 +57,10 @@ FPS_MAX_POINTS = 1 << 22                    # YOHO_FPS_MAX_POINTS
 FPS_ONE_WG_MAX = 16384                      # YOHO_FPS_ONE_WG_MAX
 FPS_BLOCK_POINTS = 1024                     # YOHO_FPS_BLOCK_POINTS
 FPS_PATHS = {"auto": 0, "one_wg": 1, "per_pick": 2}      # YOHO_FPS_AUTO, YOHO_FPS_ONE_WG, YOHO_FPS_PER_PICK
+# the entry of include/yoho_multiway.h (the information matrix of a scene's edges), kept apart for the same reason
+MULTIWAY_SYMBOLS = ["yoho_edge_information"]
+MULTIWAY_MAX_K = 64                         # YOHO_MULTIWAY_MAX_K
+MULTIWAY_MAX_SOURCE_POINTS = 1 << 26        # YOHO_MULTIWAY_MAX_SOURCE_POINTS
 
 
 class ConvW(C.Structure):
@@ -102,7 +106,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -171,7 +175,8 @@ def load_library():
     lib.yoho_sc2_scores.argtypes = [vp, vp, ci, vp, vp]
     lib.yoho_consensus_hypotheses.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]
     lib.yoho_fps.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS:
+    lib.yoho_edge_information.argtypes = [vp, vp, vp, ci, vp, ci, vp, C.c_float, vp, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -849,6 +854,27 @@ class Context:
         _check(self._lib.yoho_fps(self._h, _dev(pts, torch.float32, "pts"), m, k, int(start), FPS_PATHS[path], C.c_void_p(idx.data_ptr()),
                                   C.c_void_p(dist2.data_ptr()) if want_dist2 else None, _stream()))
         return idx, dist2
+
+    # ---- multiway registration (include/yoho_multiway.h) ---------------------------------------
+    def edge_information(self, src, soff, tgt, T, max_dist):
+        """src (S,3) f32: K source fragments one behind another, soff (K+1) int32 HOST offsets (soff[0] = 0, strictly increasing,
+        soff[K] = S), tgt (Nt,3) f32 the one target, T (K,3,4) f64 source k onto the target, 1 <= K <= MULTIWAY_MAX_K ->
+        (npairs (K) int32, rmse (K) f64, info (K,6,6) f64), device tensors: per edge the source points with a partner inside max_dist,
+        their rms distance (+inf without a pair) and the information matrix SUM G^T G, G = [I | -[p]x] over the partners p, in the
+        order (translation, rotation) (yoho_edge_information); one grid build for all K edges."""
+        soff = np.ascontiguousarray(np.asarray(soff), dtype=np.int32).reshape(-1)
+        K = soff.shape[0] - 1
+        if src.dim() != 2 or tgt.dim() != 2 or src.shape[1] != 3 or tgt.shape[1] != 3 or T.dim() != 3 or tuple(T.shape) != (K, 3, 4):
+            raise ValueError("edge_information: src (S,3), soff (K+1), tgt (Nt,3), T (K,3,4)")
+        if K >= 1 and int(soff[-1]) != src.shape[0]:
+            raise ValueError(f"edge_information: soff[K]={int(soff[-1])} must be the number of rows of src, {src.shape[0]}")
+        npairs = torch.empty((max(K, 0),), dtype=torch.int32, device=T.device)
+        rmse = torch.empty((max(K, 0),), dtype=torch.float64, device=T.device)
+        info = torch.empty((max(K, 0), 6, 6), dtype=torch.float64, device=T.device)
+        _check(self._lib.yoho_edge_information(self._h, _dev(src, torch.float32, "src"), _np_ptr(soff), K, _dev(tgt, torch.float32, "tgt"), tgt.shape[0],
+                                               _dev(T, torch.float64, "T") if K > 0 else None, float(max_dist), C.c_void_p(npairs.data_ptr()),
+                                               C.c_void_p(rmse.data_ptr()), C.c_void_p(info.data_ptr()), _stream()))
+        return npairs, rmse, info
 
     def mutual_nn(self, a, b):
         """a (Na,32), b (Nb,32) -> (M,2) int64 mutual nearest neighbours, ascending in a."""
