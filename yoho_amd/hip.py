@@ -1,5 +1,5 @@
 """ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h, include/yoho_refine.h, include/yoho_plane.h,
-include/yoho_verify.h, include/yoho_consist.h, include/yoho_keypoints.h, include/yoho_multiway.h) + a thin tensor-level wrapper.
+include/yoho_verify.h, include/yoho_consist.h, include/yoho_keypoints.h, include/yoho_multiway.h, include/yoho_fuse.h) + a thin tensor-level wrapper.
 
 PyTorch-ROCm tensors are the device-memory container only: every method passes
 ``tensor.data_ptr()`` and the current HIP stream to the C ABI.  There is NO CPU fallback: if the
@@ -61,6 +61,10 @@ FPS_PATHS = {"auto": 0, "one_wg": 1, "per_pick": 2}      # YOHO_FPS_AUTO, YOHO_F
 MULTIWAY_SYMBOLS = ["yoho_edge_information"]
 MULTIWAY_MAX_K = 64                         # YOHO_MULTIWAY_MAX_K
 MULTIWAY_MAX_SOURCE_POINTS = 1 << 26        # YOHO_MULTIWAY_MAX_SOURCE_POINTS
+# the entry of include/yoho_fuse.h (a registered scene fused into one cloud), kept apart for the same reason
+FUSE_SYMBOLS = ["yoho_fuse_clouds"]
+FUSE_MAX_K = 1024                           # YOHO_FUSE_MAX_K
+FUSE_MAX_POINTS = 1 << 26                   # YOHO_FUSE_MAX_POINTS
 
 
 class ConvW(C.Structure):
@@ -106,7 +110,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -176,7 +180,8 @@ def load_library():
     lib.yoho_consensus_hypotheses.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]
     lib.yoho_fps.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
     lib.yoho_edge_information.argtypes = [vp, vp, vp, ci, vp, ci, vp, C.c_float, vp, vp, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS:
+    lib.yoho_fuse_clouds.argtypes = [vp, vp, vp, ci, vp, vp, C.c_double, ci, ci, vp, vp, vp, vp, vp, C.c_int64, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -875,6 +880,46 @@ class Context:
                                                _dev(T, torch.float64, "T") if K > 0 else None, float(max_dist), C.c_void_p(npairs.data_ptr()),
                                                C.c_void_p(rmse.data_ptr()), C.c_void_p(info.data_ptr()), _stream()))
         return npairs, rmse, info
+
+    # ---- the fused scene (include/yoho_fuse.h) ---------------------------------------------------
+    def fuse_clouds(self, src, soff, T, voxel, min_count=1, min_frags=1, nrm=None, want_row_of=True, capacity=None):
+        """src (S,3) f32: K fragments one behind another, soff (K+1) int32 HOST offsets (soff[0] = 0, strictly increasing, soff[K] = S),
+        T (K,3,4) f64 fragment k into the scene frame, nrm (S,3) f32 or None, 1 <= K <= FUSE_MAX_K -> dict(pts (M,3) f32, normals
+        (M,3) f32 or None, count (M) int32, nfrag (M) int32, row_of (S) int32 or None, M): the voxel means of the scene in ascending
+        voxel key, a voxel kept iff it holds >= min_count points of >= min_frags fragments; row_of[e] the row of point e's voxel or -1
+        (yoho_fuse_clouds).  capacity None: a count-only call, ONE read of M, then the sized call.  capacity given: one call and no
+        read - the tensors have `capacity` rows, of which the first min(M, capacity) are written, and M is a device int64 tensor."""
+        soff = np.ascontiguousarray(np.asarray(soff), dtype=np.int32).reshape(-1)
+        K = soff.shape[0] - 1
+        if src.dim() != 2 or src.shape[1] != 3 or T.dim() != 3 or tuple(T.shape) != (K, 3, 4) or (nrm is not None and tuple(nrm.shape) != tuple(src.shape)):
+            raise ValueError("fuse_clouds: src (S,3), soff (K+1), T (K,3,4), nrm (S,3) or None")
+        if K >= 1 and int(soff[-1]) != src.shape[0]:
+            raise ValueError(f"fuse_clouds: soff[K]={int(soff[-1])} must be the number of rows of src, {src.shape[0]}")
+        dev = src.device
+        ps, pT = _dev(src, torch.float32, "src"), _dev(T, torch.float64, "T") if K > 0 else None
+        pn = _dev(nrm, torch.float32, "nrm") if nrm is not None else None
+        n_out = torch.empty((1,), dtype=torch.int64, device=dev)
+        row_of = torch.empty((src.shape[0],), dtype=torch.int32, device=dev) if want_row_of else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None          # noqa: E731
+
+        def run(cap, rows):
+            pts = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+            out_nrm = torch.empty((cap, 3), dtype=torch.float32, device=dev) if nrm is not None else None
+            count = torch.empty((cap,), dtype=torch.int32, device=dev)
+            nfrag = torch.empty((cap,), dtype=torch.int32, device=dev)
+            _check(self._lib.yoho_fuse_clouds(self._h, ps, _np_ptr(soff), K, pT, pn, float(voxel), int(min_count), int(min_frags), ptr(pts), ptr(out_nrm),
+                                              ptr(count), ptr(nfrag), ptr(rows), cap, C.c_void_p(n_out.data_ptr()), _stream()))
+            return {"pts": pts, "normals": out_nrm, "count": count, "nfrag": nfrag, "row_of": rows}
+
+        if capacity is not None:
+            out = run(int(capacity), row_of)
+            out["M"] = n_out
+            return out
+        run(0, None)
+        M = int(n_out.item())
+        out = run(M, row_of)
+        out["M"] = M
+        return out
 
     def mutual_nn(self, a, b):
         """a (Na,32), b (Nb,32) -> (M,2) int64 mutual nearest neighbours, ascending in a."""
