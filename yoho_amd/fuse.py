@@ -5,6 +5,7 @@ one mean point per voxel with the number of points and of distinct fragments beh
     fuse_registered(ctx, clouds_d, result, voxel)    the same on multiway.register_scene's result; unreached fragments (NaN poses) drop out
     write_ply / read_ply                             binary little-endian PLY with plain numpy
     write_scene_cloud(cfg, dataset)                  poses.log (multiway.write_scene) + the dataset's clouds -> scene.ply beside the log
+    clean_fused(ctx, out, clean)                     the fused rows an outlier filter keeps (yoho_amd.clean)
 """
 import os
 
@@ -108,6 +109,25 @@ def read_ply(path):
             "nfrag": np.ascontiguousarray(rec["nfrag"]) if "nfrag" in names else None}
 
 
+def filter_rows(out, sel):
+    """the rows `sel` (ascending indices) of a fused result: pts, normals, count and nfrag together; M follows; row_of, which names rows
+    of the unfiltered result, does not travel"""
+    kept = {k: (None if out.get(k) is None else out[k][sel]) for k in ("pts", "normals", "count", "nfrag")}
+    kept["M"] = int(kept["pts"].shape[0])
+    return kept
+
+
+def clean_fused(ctx, out, clean):
+    """the fused result (host arrays) without the rows yoho_amd.clean.statistical drops from its points.  clean: a dict of that function's
+    keyword arguments; max_dist has to be among them (a fused cloud's spacing is its voxel's: 4 voxels is the usual choice)."""
+    import torch
+    from . import clean as CL
+    from . import hip
+    ctx = hip.get_context() if ctx is None else ctx
+    pts = torch.from_numpy(np.ascontiguousarray(out["pts"], dtype=f32)).cuda()
+    return filter_rows(out, CL.statistical(ctx, pts, **dict(clean))["sel"].cpu().numpy())
+
+
 def _device_fuse(ctx):
     import torch
     from . import hip
@@ -119,12 +139,15 @@ def _device_fuse(ctx):
     return fuse
 
 
-def write_scene_cloud(cfg, dataset, yoho_sign='YOHO_O_MW', voxel=0.025, min_frags=1, fuse=None, max_iter=1000, min_count=1, ctx=None):
+def write_scene_cloud(cfg, dataset, yoho_sign='YOHO_O_MW', voxel=0.025, min_frags=1, fuse=None, max_iter=1000, min_count=1, ctx=None, clean=None,
+                      cleaner=None):
     """The fused cloud of one scene.  Reads result_dir(cfg, dataset, yoho_sign, max_iter)/poses.log (what multiway.write_scene left: one
     pose per fragment, nan for an unreached one) and the dataset's clouds, fuses them and writes scene.ply beside the log: the mean point
     of every voxel that >= min_count points of >= min_frags fragments fed, with both counts.
     fuse(clouds, poses, voxel, min_count, min_frags) -> dict(pts, normals or None, count, nfrag), on host arrays, replaces the device
-    pass (tests).  -> (path, that dict)"""
+    pass (tests).  clean: None, or a dict of yoho_amd.clean.statistical's keyword arguments (max_dist defaults to 4 voxels): the fused
+    rows that filter drops - strays that min_frags cannot reach where one fragment alone saw a region - are left out of the file, with
+    their normals, count and nfrag; cleaner(out, clean) -> dict replaces clean_fused (tests).  -> (path, the dict written)"""
     from .run_dataset import result_dir
     out_dir = result_dir(cfg, dataset, yoho_sign, max_iter)
     _, poses = RR_cal.read_trajectory(os.path.join(out_dir, 'poses.log'))
@@ -133,6 +156,11 @@ def write_scene_cloud(cfg, dataset, yoho_sign='YOHO_O_MW', voxel=0.025, min_frag
         raise ValueError(f"write_scene_cloud: poses.log holds {poses.shape[0]} poses, the dataset {len(clouds)} clouds")
     fuse = _device_fuse(ctx) if fuse is None else fuse
     out = fuse(clouds, poses, voxel, min_count, min_frags)
+    if clean is not None:
+        kw = dict(clean)
+        if kw.get("max_dist") is None:
+            kw["max_dist"] = 4.0 * float(voxel)
+        out = cleaner(out, kw) if cleaner is not None else clean_fused(ctx, out, kw)
     path = os.path.join(out_dir, 'scene.ply')
     write_ply(path, out["pts"], out.get("normals"), out["count"], out["nfrag"])
     return path, out

@@ -1,5 +1,6 @@
 """ctypes binding of libyoho_hip.so (include/yoho_hip.h, include/yoho_knn.h, include/yoho_trainset.h, include/yoho_refine.h, include/yoho_plane.h,
-include/yoho_verify.h, include/yoho_consist.h, include/yoho_keypoints.h, include/yoho_multiway.h, include/yoho_fuse.h) + a thin tensor-level wrapper.
+include/yoho_verify.h, include/yoho_consist.h, include/yoho_keypoints.h, include/yoho_multiway.h, include/yoho_fuse.h, include/yoho_clean.h) + a thin
+tensor-level wrapper.
 
 PyTorch-ROCm tensors are the device-memory container only: every method passes
 ``tensor.data_ptr()`` and the current HIP stream to the C ABI.  There is NO CPU fallback: if the
@@ -65,6 +66,9 @@ MULTIWAY_MAX_SOURCE_POINTS = 1 << 26        # YOHO_MULTIWAY_MAX_SOURCE_POINTS
 FUSE_SYMBOLS = ["yoho_fuse_clouds"]
 FUSE_MAX_K = 1024                           # YOHO_FUSE_MAX_K
 FUSE_MAX_POINTS = 1 << 26                   # YOHO_FUSE_MAX_POINTS
+# the entries of include/yoho_clean.h (k-NN inside a radius, the statistical outlier filter), kept apart for the same reason
+CLEAN_SYMBOLS = ["yoho_knn_within", "yoho_statistical_outliers"]
+KNN3_MAX = 32                               # YOHO_KNN3_MAX
 
 
 class ConvW(C.Structure):
@@ -110,7 +114,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -181,7 +185,9 @@ def load_library():
     lib.yoho_fps.argtypes = [vp, vp, ci, ci, ci, ci, vp, vp, vp]
     lib.yoho_edge_information.argtypes = [vp, vp, vp, ci, vp, ci, vp, C.c_float, vp, vp, vp, vp]
     lib.yoho_fuse_clouds.argtypes = [vp, vp, vp, ci, vp, vp, C.c_double, ci, ci, vp, vp, vp, vp, vp, C.c_int64, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS:
+    lib.yoho_knn_within.argtypes = [vp, vp, ci, vp, ci, C.c_float, ci, ci, vp, vp, vp, vp]
+    lib.yoho_statistical_outliers.argtypes = [vp, vp, ci, C.c_float, ci, ci, C.c_double, vp, vp, vp, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -684,6 +690,41 @@ class Context:
         _check(self._lib.yoho_nn_within(self._h, _dev(q, torch.float32, "q"), Nq, _dev(tgt, torch.float32, "tgt"), Nt, float(max_dist),
                                         C.c_void_p(idx.data_ptr()), C.c_void_p(d2.data_ptr()) if want_d2 else None, _stream()))
         return d2, idx
+
+    # ---- k-NN inside a radius and the outlier filter (include/yoho_clean.h) -------------------
+    def knn_within(self, q, tgt, max_dist, k, skip_same_row=False, want_idx=True, want_d2=True, want_count=True):
+        """q (Nq,3), tgt (Nt,3) f32, 1 <= k <= KNN3_MAX -> (d2 (Nq,k) f32, idx (Nq,k) int64, count (Nq) int32), each None when not
+        wanted: the k rows of tgt nearest to every query strictly inside max_dist, ascending by (d2, index), -1 / +inf where there are
+        fewer; count is the exact number inside the gate, not capped at k.  skip_same_row: row i is no neighbour of query i (q is tgt).
+        Without idx and d2 the call only counts (yoho_knn_within)."""
+        if q.dim() != 2 or tgt.dim() != 2 or q.shape[1] != 3 or tgt.shape[1] != 3:
+            raise ValueError("knn_within: q (Nq,3), tgt (Nt,3)")
+        Nq, Nt, k = q.shape[0], tgt.shape[0], int(k)
+        idx = torch.empty((Nq, max(k, 0)), dtype=torch.int64, device=q.device) if want_idx else None
+        d2 = torch.empty((Nq, max(k, 0)), dtype=torch.float32, device=q.device) if want_d2 else None
+        count = torch.empty((Nq,), dtype=torch.int32, device=q.device) if want_count else None
+        _check(self._lib.yoho_knn_within(self._h, _dev(q, torch.float32, "q"), Nq, _dev(tgt, torch.float32, "tgt"), Nt, float(max_dist), k,
+                                         1 if skip_same_row else 0, C.c_void_p(idx.data_ptr()) if want_idx else None,
+                                         C.c_void_p(d2.data_ptr()) if want_d2 else None, C.c_void_p(count.data_ptr()) if want_count else None, _stream()))
+        return d2, idx, count
+
+    def statistical_outliers(self, pts, max_dist, k=16, min_found=1, std_ratio=2.0, want_mean_dist=True, want_count=True):
+        """pts (N,3) f32 -> dict(keep (N) uint8, mean_dist (N) f64 or None, count (N) int32 or None, stats (4) f64 = (n_valid, mu, sigma,
+        thr), n_keep (1) int32), device tensors: mean_dist the mean distance to the min(k, count) nearest other points inside max_dist
+        (NaN with fewer than min_found of them), keep = valid and mean_dist <= mu + std_ratio * sigma (yoho_statistical_outliers)."""
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError("statistical_outliers: pts (N,3)")
+        N = pts.shape[0]
+        keep = torch.empty((N,), dtype=torch.uint8, device=pts.device)
+        mean_dist = torch.empty((N,), dtype=torch.float64, device=pts.device) if want_mean_dist else None
+        count = torch.empty((N,), dtype=torch.int32, device=pts.device) if want_count else None
+        stats = torch.empty((4,), dtype=torch.float64, device=pts.device)
+        n_keep = torch.empty((1,), dtype=torch.int32, device=pts.device)
+        _check(self._lib.yoho_statistical_outliers(self._h, _dev(pts, torch.float32, "pts"), N, float(max_dist), int(k), int(min_found), float(std_ratio),
+                                                   C.c_void_p(mean_dist.data_ptr()) if want_mean_dist else None,
+                                                   C.c_void_p(count.data_ptr()) if want_count else None, C.c_void_p(keep.data_ptr()),
+                                                   C.c_void_p(stats.data_ptr()), C.c_void_p(n_keep.data_ptr()), _stream()))
+        return {"keep": keep, "mean_dist": mean_dist, "count": count, "stats": stats, "n_keep": n_keep}
 
     def refit_matches(self, k0, k1, T, inlier_dist, iters=4):
         """k0, k1 (M,3) f64 matched keypoints, T (3,4) f64 on the device (a winner of o_score / c_ransac chains in without a host read)

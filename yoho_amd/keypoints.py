@@ -6,6 +6,7 @@ The reference draws its 5000 keypoints uniformly over the scan points (simple_yo
     kidx, dist2 = keypoints.select(ctx, pc_d, 5000, voxel=0.025)      # cloud indices in pick order, on the device
     keypoints.write_keypoints(dataset)                                # Keypoints/*.txt + Keypoints_PC/*.npy for an own dataset
     yoho_extractor(..., keypoints="fps")                              # the one-cloud API with spread keypoints
+    keypoints.select(ctx, pc_d, 5000, voxel=0.025, clean={})          # strays filtered out of the candidates first (yoho_amd.clean)
 
 Every pick is a prefix of every longer selection from the same start, so nkpts only cuts the list.  Nothing here draws from a random
 generator.
@@ -34,10 +35,28 @@ def candidates(ctx, pc_d, voxel):
     return sel, ctx.rotate_select(pc_d, None, sel)
 
 
-def select(ctx, pc_d, nkpts, voxel=None, start=0):
+def clean_candidates(ctx, sel, pts, voxel, clean):
+    """the candidates that yoho_amd.clean.statistical keeps: clean is a dict of its keyword arguments, max_dist defaulting to 4 voxels
+    (it has to be given when voxel is None) -> (sel, pts) of the kept candidates, in their order"""
+    from . import clean as CL
+    kw = dict(clean)
+    if kw.get("max_dist") is None:
+        if voxel is None:
+            raise ValueError("select: clean needs max_dist when there is no voxel to take it from")
+        kw["max_dist"] = 4.0 * float(voxel)
+    kept = CL.statistical(ctx, pts, **kw)["sel"]
+    return sel[kept], pts[kept].contiguous()
+
+
+def select(ctx, pc_d, nkpts, voxel=None, start=0, clean=None):
     """k = min(nkpts, candidates) spread keypoints of pc_d (n,3) f64 on the device -> (kidx (k) int64 cloud indices in pick order,
-    dist2 (k) f32), device tensors: farthest-point sampling (Context.fps) over candidates(ctx, pc_d, voxel), from candidate `start`."""
+    dist2 (k) f32), device tensors: farthest-point sampling (Context.fps) over candidates(ctx, pc_d, voxel), from candidate `start`.
+    clean: None, or a dict of yoho_amd.clean.statistical's keyword arguments ({}: its defaults) - farthest-point sampling seeks out
+    whatever lies far from everything, a stray first of all, so the candidates go through the outlier filter before the selection
+    (one more host read); `start` then counts the kept candidates."""
     sel, pts = candidates(ctx, pc_d, voxel)
+    if clean is not None:
+        sel, pts = clean_candidates(ctx, sel, pts, voxel, clean)
     k = max(0, min(int(nkpts), sel.shape[0]))
     idx, dist2 = ctx.fps(pts, k, start=start)
     return sel[idx], dist2
@@ -50,27 +69,29 @@ def coverage_radius(ctx, pts_f32, keys_f32):
     return float(np.sqrt(np.float64(d2.max().item())))
 
 
-def _select_host(ctx, pc, nkpts, voxel):
+def _select_host(ctx, pc, nkpts, voxel, clean=None):
     pc_d = torch.from_numpy(np.ascontiguousarray(np.asarray(pc, dtype=np.float64))).cuda()
-    return select(ctx, pc_d, nkpts, voxel=voxel)[0].cpu().numpy()
+    return select(ctx, pc_d, nkpts, voxel=voxel, clean=clean)[0].cpu().numpy()
 
 
-def write_keypoints(dataset, nkpts=5000, voxel=0.025, ctx=None, overwrite=False, selector=None):
+def write_keypoints(dataset, nkpts=5000, voxel=0.025, ctx=None, overwrite=False, selector=None, clean=None):
     """Spread keypoints for every cloud of an EvalDataset that has no `Keypoints/cloud_bin_{k}Keypoints.txt` yet (overwrite=True: for
     every cloud): the index file, np.savetxt of the cloud indices in pick order, and `Keypoints_PC/cloud_bin_{k}Keypoints.npy`,
     pc[indices] - the two files ThrDMatchPartDataset.get_kps reads, in its formats, so that it never reaches its random draw.  A cloud
     whose index file exists is left alone.  selector(pc, nkpts, voxel) -> indices replaces the device selection (tests).
+    clean: select's; a selector is then called as selector(pc, nkpts, voxel, clean=clean).
     -> the ids of the clouds written."""
     if selector is None:
         ctx = hip.get_context() if ctx is None else ctx
-        selector = lambda pc, n, v: _select_host(ctx, pc, n, v)      # noqa: E731
+        selector = lambda pc, n, v, clean=None: _select_host(ctx, pc, n, v, clean)      # noqa: E731
     written = []
     for cid in dataset.get_cloud_ids():
         k = int(cid)
         if os.path.exists(dataset.kps_fn[k]) and not overwrite:
             continue
         pc = dataset.get_pc(cid)
-        key_idxs = np.asarray(selector(pc, nkpts, voxel), dtype=np.int64).reshape(-1)
+        picked = selector(pc, nkpts, voxel) if clean is None else selector(pc, nkpts, voxel, clean=clean)
+        key_idxs = np.asarray(picked, dtype=np.int64).reshape(-1)
         make_non_exists_dir(os.path.dirname(dataset.kps_fn[k]))
         np.savetxt(dataset.kps_fn[k], key_idxs)
         make_non_exists_dir(os.path.dirname(dataset.kps_pc_fn[k]))

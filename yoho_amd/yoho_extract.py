@@ -69,14 +69,18 @@ KEYPOINT_MODES = ("random", "fps")
 
 class yoho_extractor():
     def __init__(self, fcgf_ckpt='model/Backbone/best_val_checkpoint.pth', yoho_ckpt='model/PartI_train/model_best.pth',
-                 fcgf=None, so3_dir=None, keypoints="random", keypoint_voxel=None):
+                 fcgf=None, so3_dir=None, keypoints="random", keypoint_voxel=None, keypoint_clean=None):
         """keypoints: "random" - the reference's np.random.permutation(len(pc))[0:nkpts] on numpy's global generator -, or "fps" -
         farthest-point sampling on the device (yoho_amd.keypoints.select) over the first point of every voxel of
         keypoint_voxel (None: the voxel_size of the call), from candidate 0: no draw from any generator, keypoints in pick order, a
-        smaller nkpts a prefix of a larger one."""
+        smaller nkpts a prefix of a larger one.  keypoint_clean ("fps" only): a dict of yoho_amd.clean.statistical's keyword arguments -
+        the candidates that filter drops are never picked (yoho_amd.keypoints.select's `clean`); None: no filter."""
         if keypoints not in KEYPOINT_MODES:
             raise ValueError(f"yoho_extractor: keypoints must be one of {KEYPOINT_MODES}, got {keypoints!r}")
+        if keypoint_clean is not None and keypoints != "fps":
+            raise ValueError(f"yoho_extractor: keypoint_clean filters the candidates of keypoints=\"fps\"; keypoints={keypoints!r} draws from the whole cloud")
         self.keypoints = keypoints
+        self.keypoint_clean = None if keypoint_clean is None else dict(keypoint_clean)
         self.keypoint_voxel = keypoint_voxel
         self.ctx = hip.get_context(so3_dir=so3_dir)
         self.grs = self.ctx.tables.R64
@@ -149,7 +153,8 @@ class yoho_extractor():
 
         def prepare(pc_d):                         # on lane 0's stream
             if fps:
-                kidx_d = KP.select(lanes[0][0], pc_d, nkpts, voxel=voxel_size if self.keypoint_voxel is None else self.keypoint_voxel)[0]
+                kidx_d = KP.select(lanes[0][0], pc_d, nkpts, voxel=voxel_size if self.keypoint_voxel is None else self.keypoint_voxel,
+                                   clean=self.keypoint_clean)[0]
                 kpts = None
             else:
                 kpts_index = np.random.permutation(len(pc))[0:nkpts]
@@ -253,7 +258,8 @@ class yoho_extractor():
         # a backbone with run() only: the reference's host loop
         if self.keypoints == "fps":
             pc_d = torch.from_numpy(np.ascontiguousarray(np.asarray(pc, dtype=np.float64))).cuda()
-            kpts_index = KP.select(self.ctx, pc_d, nkpts, voxel=voxel_size if self.keypoint_voxel is None else self.keypoint_voxel)[0].cpu().numpy()
+            kpts_index = KP.select(self.ctx, pc_d, nkpts, voxel=voxel_size if self.keypoint_voxel is None else self.keypoint_voxel,
+                                   clean=self.keypoint_clean)[0].cpu().numpy()
         else:
             kpts_index = np.random.permutation(len(pc))[0:nkpts]
         kpts = pc[kpts_index]
