@@ -265,10 +265,26 @@ int yoho_bn_relu_backward(yoho_ctx* ctx, const float* x, const float* y, const f
                           const float* mean, const float* rstd, int batch_stats, float* dx, float* dgamma, float* dbeta, void* stream);
 
 /* ---- FCGF backbone (reference fcgf_model/resunet.py ResUNet2 family, simple_yoho/fcgf_feat.py) ------------------------
- * Sparse 3-D ResUNet forward pass, fp32.  channels / tr_channels = CHANNELS / TR_CHANNELS of the model class (index 0
- * unused), e.g. ResUNetBN2C: {0,32,64,128,256} / {0,64,64,64,128}.  tensors: host pointers to the state_dict entries in
- * the model's registration order with the num_batches_tracked entries left out (conv1.kernel, norm1.bn.{weight,bias,
- * running_mean,running_var}, block1.conv1.kernel, ...; yoho_amd.weights.fcgf_spec()). */
+ * Sparse 3-D ResUNet forward pass; fp32 in and out, fp32 between the layers.  channels / tr_channels = CHANNELS /
+ * TR_CHANNELS of the model class (index 0 unused), e.g. ResUNetBN2C: {0,32,64,128,256} / {0,64,64,64,128}.  tensors: host
+ * pointers to the state_dict entries in the model's registration order with the num_batches_tracked entries left out
+ * (conv1.kernel, norm1.bn.{weight,bias,running_mean,running_var}, block1.conv1.kernel, ...; yoho_amd.weights.fcgf_spec()).
+ *
+ * Arithmetic.  By default every convolution with input and output channels in multiples of 32 (all but the first, whose input is
+ * the occupancy of the kernel region) is a 2-way fp16 split on v_mfma_f32_32x32x16_f16 with fp32 accumulation: the activation
+ * as 16 x = hi + lo, split in registers, the weights scaled so that the layer's largest lies in [512, 1024) and split when they
+ * are loaded, three of the four plane products (error <= 3*2^-22 per product).  Between the two limits below the result is as
+ * far from a float64 evaluation as an fp32 one is (measured: profiles/precision.md, backbone section).
+ *   Upper limit: |activation| < 4094 in front of every such convolution (a trained checkpoint's are O(1-10)).  From 4095 on
+ *     hi is infinite and lo NaN: every output row such a value reaches through the kernel maps comes back as NaN, and every row
+ *     that comes back finite is right.  There is no device flag and no automatic repeat for the backbone (yoho_range_status
+ *     covers PartI / PartII only): a caller that cannot rule the range out checks the rows for NaN.
+ *   Lower limit: below |x| ~ 2^-7 the lo plane is subnormal in fp16 (the hardware keeps it; nothing is flushed), so the
+ *     error of an activation stops being relative and stays at about 2^-29.  With ALL activations of a network scaled by s the
+ *     worst row's error on unit rows is about 5e-7 for s >= 2^-4 (plane rounding alone; fp32 accumulation adds about 1e-6)
+ *     and grows like 1/s below: 5e-6 at 2^-8, 6e-5 at 2^-12, 1e-3 at 2^-16.
+ * A context created with YOHO_FCGF=f32 in the environment loads the fp32 MFMA kernels (v_mfma_f32_32x32x2_f32) instead: fp32
+ * exponent range and no lower limit, at the fp32 MFMA rate.  That is the path to repeat a pass on. */
 typedef struct yoho_fcgf_config {
     int channels[5];
     int tr_channels[5];

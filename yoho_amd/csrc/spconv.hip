@@ -29,6 +29,14 @@ __device__ __forceinline__ int sp_next_offset(unsigned& mask) {
     return k;
 }
 
+// The ReLU of every epilogue: IEEE maximum (one v_maximum3_f32), which hands a NaN on.  Not fmaxf: that answers a NaN with 0, and a NaN
+// is what an activation past the range of the fp16 planes (split_pair_sp) makes of the rows it reaches - it has to arrive at the caller.
+// Every other value gets the bits fmaxf gave it (-0 -> +0 included).
+__device__ __forceinline__ float sp_relu(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+// the same as a maximum with a floor picked outside the loop: 0, or -inf where the layer has no ReLU (the identity, NaN included) - no
+// branch and no select per value in the fine-level epilogue
+__device__ __forceinline__ float sp_floor(float v, float lo) { return __builtin_elementwise_maximum(v, lo); }
+
 // NCB = 32-channel output blocks per wave.  SPLIT = false: every wave of the workgroup owns its own 32 output rows.
 // SPLIT = true (coarse levels: few rows, many channels): the four waves share one 32-row tile and split the
 // (kernel offset, channel chunk) loop four ways; the partial sums meet in LDS and are added in wave order.
@@ -117,7 +125,7 @@ __global__ __launch_bounds__(256) void spconv_kernel(SpConvArgs a) {
             if (orow < a.nout) {
                 float v = acc[cb][r] * s + t;
                 if (a.res) v += a.res[(size_t)orow * a.ldres + a.rcoff + co];
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = sp_relu(v);
                 a.out[(size_t)orow * a.ldout + a.ocoff + co] = v;
             }
         }
@@ -126,7 +134,7 @@ __global__ __launch_bounds__(256) void spconv_kernel(SpConvArgs a) {
 
 // fp16x2 split variant (same decomposition as spconv_kernel): every product as lo*hi + hi*lo + hi*hi on
 // v_mfma_f32_32x32x16_f16 with fp32 accumulation (3 MFMAs at 16x the fp32-MFMA rate, error <= 3 * 2^-22 per product).
-// The gathered fp32 rows are split in registers (x * 16 = hi + lo; activations must stay below 4094); the weights are
+// The gathered fp32 rows are split in registers (x * 16 = hi + lo; activations must stay below 4094: from 4095 on hi is infinite, lo and the row's sums NaN); the weights are
 // split once at load time and stored in B-fragment order
 //     Wh[k][chunk32][K16 step 2][plane 2][cout block][lane = 32 kg + j][8]  =  W[k][32 chunk + 16 step + 8 kg + e][32 cb + j]
 // so a fragment is one 16-byte load per lane.
@@ -291,7 +299,7 @@ __global__ __launch_bounds__(256) void spconv16s_kernel(SpConvArgs a) {
             if (orow >= 0) {
                 float v = acc[cb][r] * s + t;
                 if (a.res) v += a.res[(size_t)orow * a.ldres + a.rcoff + co];
-                if (a.relu) v = fmaxf(v, 0.f);
+                if (a.relu) v = sp_relu(v);
                 a.out[(size_t)orow * a.ldout + a.ocoff + co] = v;
             }
         }
@@ -441,6 +449,7 @@ __device__ __forceinline__ void spconv16w_body(const SpConvArgs& a) {
     __syncthreads();                                                      // every wave is done with the stage buffers
     float* et = reinterpret_cast<float*>(smem) + w * 32 * EPI_LD;
     const int er = lane >> 3, ep = lane & 7;                              // row within a group of eight, 4-channel piece
+    const float relu_lo = a.relu ? 0.f : -__builtin_inff();
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
         if (cb) __builtin_amdgcn_wave_barrier();
@@ -461,7 +470,7 @@ __device__ __forceinline__ void spconv16w_body(const SpConvArgs& a) {
                     const float4 rr = *reinterpret_cast<const float4*>(a.res + (size_t)orow * a.ldres + a.rcoff + co);
                     v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w;
                 }
-                if (a.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+                v.x = sp_floor(v.x, relu_lo); v.y = sp_floor(v.y, relu_lo); v.z = sp_floor(v.z, relu_lo); v.w = sp_floor(v.w, relu_lo);
                 size_t drow = (size_t)orow;
                 if constexpr (NCB == 1) {
                     if (a.norm) {
@@ -569,7 +578,7 @@ __global__ __launch_bounds__(256) void heads_fused_kernel(HeadsArgs a) {
                 for (int r = 0; r < 16; ++r) {
                     float v = acc1[cb][r];
                     v = v * sc + sh;
-                    et[((r & 3) + 8 * (r >> 2) + 4 * h) * LD1 + cb * 32 + li] = fmaxf(v, 0.f);
+                    et[((r & 3) + 8 * (r >> 2) + 4 * h) * LD1 + cb * 32 + li] = sp_relu(v);
                 }
         }
         __builtin_amdgcn_wave_barrier();
@@ -656,7 +665,7 @@ __global__ __launch_bounds__(256) void spconv_small_kernel(SpConvArgs a) {
     }
     float v = acc * (a.aff_s ? a.aff_s[co] : 1.f) + (a.aff_t ? a.aff_t[co] : 0.f);
     if (a.res) v += a.res[(size_t)row * a.ldres + a.rcoff + co];
-    if (a.relu) v = fmaxf(v, 0.f);
+    if (a.relu) v = sp_relu(v);
     a.out[(size_t)row * a.ldout + a.ocoff + co] = v;
 }
 

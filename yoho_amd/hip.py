@@ -404,7 +404,9 @@ class Context:
     # ---- FCGF backbone ------------------------------------------------------------------------
     def load_fcgf(self, sd, channels=(0, 32, 64, 128, 256), tr_channels=(0, 64, 64, 64, 128), out_channels=32, conv1_kernel_size=7,
                   in_channels=1, normalize_feature=True, owner=None):
-        """sd: FCGF backbone state_dict (torch tensors or ndarrays); architecture parameters as in fcgf_model/resunet.py."""
+        """sd: FCGF backbone state_dict (torch tensors or ndarrays); architecture parameters as in fcgf_model/resunet.py.
+        The convolutions run as fp16x2 split MFMA products (fp32-accurate for activations between about 2^-7 and 4094, include/yoho_hip.h
+        at the FCGF section) unless the context was created with YOHO_FCGF=f32 in the environment: then the fp32 MFMA kernels are loaded."""
         self.fcgf_owner = owner
         sd = _weights.to_numpy_state_dict(sd)
         spec = _weights.fcgf_spec(tuple(channels), tuple(tr_channels), out_channels, conv1_kernel_size, in_channels)
@@ -470,14 +472,17 @@ class Context:
         return out
 
     def fcgf_forward(self, coords):
-        """coords (n,3) int32 cuda, distinct voxels -> (n, out_channels) f32 unit rows."""
+        """coords (n,3) int32 cuda, distinct voxels -> (n, out_channels) f32 unit rows.  fp16x2 split products by default: a row reached by
+        an activation of 4095 or more comes back as NaN (every finite row is right); there is no automatic repeat - a context created
+        under YOHO_FCGF=f32 has the fp32 exponent range."""
         n = coords.shape[0]
         out = torch.empty((n, getattr(self, "_fcgf_out", 32)), dtype=torch.float32, device=coords.device)
         _check(self._lib.yoho_fcgf_forward(self._h, _dev(coords, torch.int32, "coords"), n, C.c_void_p(out.data_ptr()), _stream()))
         return out
 
     def fcgf_forward_batch(self, coords_list):
-        """several clouds ((n_b,3) int32 cuda each) in one pass -> list of (n_b, out_channels) feature tensors."""
+        """several clouds ((n_b,3) int32 cuda each) in one pass -> list of (n_b, out_channels) feature tensors (arithmetic and range as
+        fcgf_forward)."""
         nb = len(coords_list)
         off = np.zeros(nb + 1, dtype=np.int32)
         off[1:] = np.cumsum([c.shape[0] for c in coords_list])
