@@ -138,8 +138,8 @@ def test_constructed_ties(ctx):
 def test_ties_that_only_the_rounded_l2_distance_has(ctx, D):
     """D2 = 2e-15 at the LOWER index and 1e-15 at the higher one: both give fl(D2 + 1e-7) = 1e-7f, i.e. equal L2 distance bits - under
     L2 the lower index comes first, under SquareL2 the smaller D2 (the higher index).  Once with both indices on one lane of the
-    search (congruent mod 16) and once not, in the first tile of 256 targets and in the second.  (yoho_nn_search is not asked here:
-    its relative shortcut on D2 calls such a pair clearly different)"""
+    search (congruent mod 16) and once not, in the first tile of 256 targets and in the second.  Column 0 is yoho_nn_search's answer
+    here too (tests/test_gpu_nn.py has its own cases)."""
     a = np.zeros((5, D), np.float32)
     for base in (0, 256):
         for lo, hi in ((base + 2, base + 18), (base + 2, base + 4)):
@@ -157,7 +157,7 @@ def test_ties_that_only_the_rounded_l2_distance_has(ctx, D):
                 _, i = search(ctx, cu(a), cu(b), k, True)
                 assert (i == want_sq).all(), (D, lo, hi, k, i[0])
             for sq in (False, True):
-                check_against_ref(ctx, a, b, (1, 2, 3), sq, ("rounded ties", D, lo, hi), nn_column=False)
+                check_against_ref(ctx, a, b, (1, 2, 3), sq, ("rounded ties", D, lo, hi), nn_column=True)
 
 
 def test_result_ignores_switches_scratch_and_call_count(hip):

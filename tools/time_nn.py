@@ -6,6 +6,10 @@
     (utils/knn_search.py:68-106 written out with torch ops; its per-chunk copies to the host are left out, which favours it).
 
     python tools/time_nn.py [--repeats 5] [--window 0.3] [--out profiles/knn_search_timings.md]
+    python tools/time_nn.py --brute-only [--lib other/libyoho_hip.so]      # the brute-force searches alone (nn_kernel's family):
+                                                                           # yoho_nn_search 'L2' at 5000 x 5000 x 32 and x 3, mutual NN
+                                                                           # with the pre-filter off; --lib times another build of the
+                                                                           # library (a parent commit's) in a process of its own
 
 One process, every variant warmed up, HIP events on the stream, a timed window repeats the call until it lasts `--window` seconds (a
 single call is tens of microseconds and would measure the launch), the variants alternate `--repeats` times; median and [min, max] of
@@ -81,13 +85,38 @@ def main():
     ap.add_argument("--window", type=float, default=0.3, help="seconds a timed window lasts at least")
     ap.add_argument("--out", default=None, help="also write the tables to this file")
     ap.add_argument("--skip-3d", action="store_true")
+    ap.add_argument("--brute-only", action="store_true", help="only the brute-force searches: nn_search 'L2' at D = 32 and D = 3, mutual NN without the pre-filter")
+    ap.add_argument("--lib", default=None, help="load this build of libyoho_hip.so instead of the tree's")
     args = ap.parse_args()
+    if args.lib:
+        hip._LIB_PATH = os.path.abspath(args.lib)
     c = hip.Context(0)
     probe = ClockProbe(c, us=200)
     lines = [f"device: {torch.cuda.get_device_name(0)}; {args.repeats} alternated windows of >= {args.window} s per variant"]
 
     pr = synth.make_pair(5000, seed=10)
     a, b = cu(np.mean(pr["feat0"], -1)), cu(np.mean(pr["feat1"], -1))
+    if args.brute_only:
+        rs = np.random.RandomState(3)
+        q3, t3 = cu(rs.rand(5000, 3).astype(np.float32) * 3), cu(rs.rand(5000, 3).astype(np.float32) * 3)
+        c.set_nn_grid(0)
+        c.set_nn_prefilter(False)
+        variants = [(("yoho_nn_search, 5000 x 5000 x 32, 'L2'", 1), lambda: c.nn_search(a, b, want_dist=True)),
+                    (("yoho_nn_search, 5000 x 5000 x 3, 'L2'", 1), lambda: c.nn_search(q3, t3, want_dist=True)),
+                    (("mutual_nn, brute force, 5000 x 5000 x 32", "-"), lambda: c.mutual_nn(a, b))]
+        res = alternate(variants, args.repeats, args.window, probe)
+        c.set_nn_prefilter(True)
+        lines[0] += f"; library {hip._LIB_PATH if args.lib else 'of the tree'}"
+        table("brute-force searches", res, lines)
+        lines.append("")
+        lines.append(f"shader clock while the windows ran (one-wave probes of 200 us): {probe.summary()}")
+        text = "\n".join(lines)
+        print(text)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     variants = []
     for on in (True, False):
         def mutual(on=on):

@@ -27,9 +27,9 @@
 //   * SquareL2: T = r.   L2: the candidate's fp32 sum s = fl(D2 + 1e-7) is compared, the f64 square root is taken only below T.
 //     sqrt and its rounding are monotone, and s >= T = fl(fl(r r)(1 + 1e-6)) >= r^2 (1 + 8e-7) gives sqrt(s) >= r (1 + 3e-7) > r,
 //     i.e. a rounded distance >= r: rejected rightly.  The test is on the SUM, so it holds at every magnitude - D2 = 1e-15 and
-//     2e-15 both give s = 1e-7f, equal distance bits, a tie that the index decides (a relative test on D2, as nn_kernel's
-//     `d2 < best (1 - 1e-6)`, would call them clearly different).  Sums in the band [r^2, T) pay a square root for
-//     nothing; that is all.
+//     2e-15 both give s = 1e-7f, equal distance bits, a tie that the index decides (a relative test on D2 would call them clearly
+//     different; nn_kernel / nn32seg_kernel had one and now decide on the sums too: nn_closer, nnmath.h).  Sums in the band
+//     [r^2, T) pay a square root for nothing; that is all.
 //   * NaN sums are folded to the one quiet NaN 0x7FC00000 (above +inf in integer order: NaN sorts last), so the keys stay totally
 //     ordered and a row of NaN / inf still gets k distinct in-range indices.
 // A segment's 16 lanes write its k keys to the workspace [Ns][nseg][k]; knn_merge_kernel (16 lanes per row, the same insertion)

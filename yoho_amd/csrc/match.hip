@@ -32,9 +32,9 @@ __global__ __launch_bounds__(256) void nn_kernel(const float* __restrict__ src, 
     const int rowc = row < Ns ? row : Ns - 1;
 #pragma unroll
     for (int k = 0; k < D; ++k) a[k] = src[(size_t)rowc * D + k];
-    // best holds the squared distance.  For the 'L2' form the reference compares sqrt(D2 + 1e-7) (first minimum);
-    // sqrt is monotone, so a later candidate can only win with a smaller D2, and the correctly rounded sqrt
-    // (computed in f64) is evaluated only when the two D2 are close enough to round to the same distance.
+    // best holds the squared distance.  For the 'L2' form the reference compares sqrt(D2 + 1e-7) (first minimum): a later
+    // candidate wins only with a strictly smaller ROUNDED distance, which nn_closer (nnmath.h) decides on the sums D2 + 1e-7 -
+    // the correctly rounded sqrt (computed in f64) is evaluated only when the two sums are not proven 9e-7 apart.
     auto dist_of = [](float d2) -> float { return dist_of_f32(d2); };
     float best = __builtin_inff();
     int besti = 0;
@@ -45,9 +45,7 @@ __global__ __launch_bounds__(256) void nn_kernel(const float* __restrict__ src, 
         __syncthreads();
         for (int t = sp; t < nt; t += NN_SPLIT) {
             const float d2 = dist2_f32<D>(a, tile + t * D);
-            if (d2 < best) {
-                if (SQUARED || d2 < best * (1.0f - 1e-6f) || dist_of(d2) < dist_of(best)) { best = d2; besti = t0 + t; }
-            }
+            if (nn_closer<SQUARED>(d2, best)) { best = d2; besti = t0 + t; }
         }
     }
     if (!SQUARED) best = dist_of(best);
@@ -132,12 +130,8 @@ __global__ __launch_bounds__(256) void nn32seg_kernel(const float* __restrict__ 
                 for (int k = 0; k < D; ++k) b[k] = tile[t * D + k];
             }
             const float d0 = dist2_f32<D>(a0, b), d1 = dist2_f32<D>(a1, b);
-            if (d0 < best0) {
-                if (SQUARED || d0 < best0 * (1.0f - 1e-6f) || dist_of(d0) < dist_of(best0)) { best0 = d0; bi0 = t0 + t; }
-            }
-            if (d1 < best1) {
-                if (SQUARED || d1 < best1 * (1.0f - 1e-6f) || dist_of(d1) < dist_of(best1)) { best1 = d1; bi1 = t0 + t; }
-            }
+            if (nn_closer<SQUARED>(d0, best0)) { best0 = d0; bi0 = t0 + t; }
+            if (nn_closer<SQUARED>(d1, best1)) { best1 = d1; bi1 = t0 + t; }
         }
     }
     if (!SQUARED) { best0 = dist_of(best0); best1 = dist_of(best1); }

@@ -38,6 +38,28 @@ __device__ __forceinline__ float dist2_f32(const float* a, const float* b) {
 // pdist 'L2': sqrt(D2 + 1e-7) as torch evaluates it on fp32 (utils/knn_search.py:17-20)
 __device__ __forceinline__ float dist_of_f32(float d2) { return (float)sqrt((double)__fadd_rn(d2, 1e-7f)); }
 
+// The first-minimum rule of the brute-force searches (nn_kernel, nn32seg_kernel): does a LATER target with squared distance d2
+// replace the best so far (squared distance `best`)?  SquareL2: d2 < best.  L2: only a strictly smaller ROUNDED distance does, and
+// what decides are the sums s = fl(d2 + e), sb = fl(best + e), e = 1e-7f, that the square root is taken of, as in knn.hip - a
+// relative test on d2 itself (these kernels had `d2 < best (1 - 1e-6)`) is wrong once d2 is small against e: D2 = 1e-9 and
+// 1e-9 (1 - 8e-6) are far apart relatively and give the same distance bits.  Addition, square root and rounding are monotone, so
+// d2 >= best cannot win.  Below that, the roots are skipped where the sums are PROVEN more than 9e-7 apart, by one fma on d2:
+// with c = fl(1 - 1e-6) = 1 - 1.0133e-6, k = 1.1e-13 >= 9e-7 e and u = 2^-24,
+//   d2 < t = fl(best c - k)  =>  t > 0 and d2 + e < (best c - k)(1 + u) + e <= (best + e)(1 - 9e-7)      [c (1 + u) <= 1 - 9e-7]
+//   =>  s / sb <= (1 - 9e-7)(1 + u) / (1 - u) < 1 - 7.8e-7  =>  sqrt(s) < sqrt(sb)(1 - 3.9e-7)
+//   =>  fl(sqrt(s)) <= sqrt(s)(1 + u) < sqrt(sb)(1 - u) <= fl(sqrt(sb)):  strictly smaller.
+// Everything else below `best` pays the two f64 roots and their rounded values decide; for best <= 1.1e-13 that is every such d2
+// (t <= 0).  The test costs what the old one did (an fma for a multiplication): in nn32seg_kernel some lane of a wave is below its
+// best at almost every step, so whatever stands behind `d2 < best` is paid per step (forming both sums there: + 2 % at D = 3,
+// profiles/nn_ties.md).  best = +inf (nothing seen yet) takes any finite d2; a NaN d2 never wins.
+template <bool SQUARED>
+__device__ __forceinline__ bool nn_closer(float d2, float best) {
+    if (!(d2 < best)) return false;
+    if (SQUARED) return true;
+    if (d2 < fmaf(best, 1.0f - 1e-6f, -1.1e-13f)) return true;
+    return dist_of_f32(d2) < dist_of_f32(best);
+}
+
 // one coordinate of keys @ Rg^T in f64 (YOHO_testset.py:157) and the f64 squared distance to a widened f32 point
 struct GnMat3 { double m[9]; };
 __device__ __forceinline__ double rotate_key_f64(const double* kk, const double* row) {
