@@ -7,7 +7,7 @@ BEFORE the exact distance decides, so that the CPU suite can show the inputs rea
 
   * `rounded_tie_targets` / `mutual_tie_case`: two targets whose D2 differ by more than 1e-6 relative and whose 'L2' distances
     sqrt(D2 + 1e-7) have the same bits - the reference answers the lower index, a rule that looks at D2 alone the later one
-    (`kernel_rule_before_fix`: the 16-lane rule nn_kernel / nn32seg_kernel had; `kernel_rule`: the one they have now);
+    (`kernel_rule_before_fix`: the 16-lane rule nn32seg_kernel (one and two rows per thread) had; `kernel_rule`: the one they have now);
   * `band_case`: a query whose true neighbour loses against a rival in the fp16 Gram scores of the matcher's pre-filter
     (csrc/matchf.hip) by a large share of the candidate band - every magnitude sits at an fp16 rounding midpoint;
     `emu_prefilter` restates those scores, the row minimum and `band_of`, with the band's leading constant and the set its maximum
@@ -24,7 +24,7 @@ import yoho_oracle as orc  # noqa: E402
 TIE_SCALES = (4.47e-8, 1.2e-5, 2.5e-5)      # distance of the tie pair from the zero query: D2 = 2e-15, 1.4e-10, 6.3e-10
 TIE_GAP = 4e-6                              # relative difference of the two distances (8e-6 of D2: the old shortcut's 1e-6 calls it clear)
 NN_LANES = 16                               # targets t, t + 16, t + 32, ... of a segment are visited by one thread
-NN_TILE = 256                               # target rows per LDS tile of nn_kernel / nn32seg_kernel
+NN_TILE = 256                               # target rows per LDS tile of nn32seg_kernel (NN_TT, csrc/nntile.h)
 SEG_PAIRS = 1 << 20                         # Ns * Nt from which yoho_nn_search / yoho_mutual_nn take the segmented / pre-filter path
 F1 = np.float32(1.0)
 
@@ -96,7 +96,8 @@ def tie_sources(D, Ns, rows=(0, 7, 15, 16, 31, -1)):
 
 
 def seg_len(Ns, Nt, nCU):
-    """launch_nn32seg's cut of the targets (csrc/match.hip): -> (segLen, nseg)"""
+    """nn_segment_plan's cut of the targets (csrc/nntile.h; 32 rows per workgroup, no single-segment rule: launch_nn32seg's call):
+    -> (segLen, nseg)"""
     rb = (Ns + 31) // 32
     nseg = (4 * nCU + rb - 1) // rb
     maxseg = (Nt + 63) // 64
@@ -107,7 +108,7 @@ def seg_len(Ns, Nt, nCU):
 
 
 def tie_placements(Nt, seg=None):
-    """{name: (lo, hi)} inside Nt targets cut into segments of `seg` rows (None: one segment, nn_kernel).  One thread visits the
+    """{name: (lo, hi)} inside Nt targets cut into segments of `seg` rows (None: one segment, the one-row nn32seg_kernel).  One thread visits the
     targets of a segment that are congruent mod 16, tile after tile of 256 from the segment's start."""
     seg = Nt if seg is None or seg > Nt else seg
     out = {"i, i + 16": (2, 18), "i, i + 256": (2, 2 + NN_TILE), "i, i + 2": (2, 4),
@@ -131,7 +132,7 @@ def _dist(d2):
 
 def _lanes(d2_row, take, seg=None):
     """the per-lane scan (targets sp, sp + 16, ... of a segment in order, `take(d2, best)` decides) and the merge of the lanes of
-    all segments by (rounded distance, index): the shape of nn_kernel (seg=None) and nn32seg_kernel"""
+    all segments by (rounded distance, index): the shape of nn32seg_kernel with one row per thread (seg=None) and with two"""
     d2_row = np.asarray(d2_row, np.float32)
     n = len(d2_row)
     seg = n if seg is None or seg > n else seg
@@ -150,7 +151,7 @@ def _lanes(d2_row, take, seg=None):
 
 
 def kernel_rule_before_fix(d2_row, seg=None):
-    """'L2' index of nn_kernel / nn32seg_kernel as they were: a later target of the lane wins without a square root when
+    """'L2' index of nn32seg_kernel (either row count) as it was: a later target of the lane wins without a square root when
     d2 < best (1 - 1e-6), a relative test on D2"""
     c = np.float32(F1 - np.float32(1e-6))
 

@@ -700,6 +700,45 @@ def test_group_transfer_batch_equals_per_copy_calls(hip, tables):
         c.group_transfer_batch(pts, kidx, Rs, ds, ft, 58, out)          # 58 + 4 copies > 60 group elements
 
 
+def test_group_transfer_batch_spans_two_launches(hip, tables):
+    """17 copies: the batch is cut into launches of 16, so copy 16 runs in a second launch whose tables, lists and output column
+    are addressed from the offsets 16 * cap, 16 * mmax, 16 * K and g0 + 16.  K = 70 leaves the last query workgroup half empty; in
+    every copy some queries are settled by the 5^3 block and some go through the fallback list (checked on the CPU below)."""
+    c = hip.Context()
+    rs = np.random.RandomState(11)
+    nb, K, g0, cell = 17, 70, 20, 0.05
+    pts_h = rs.rand(4000, 3) * 1.5
+    kidx_h = rs.permutation(4000)[:K].astype(np.int64)
+    pts_h[kidx_h[:5]] += 10.0                                            # far outside the cloud's box: nothing within 2 cells
+    sizes = (400, 131, 257, 333, 190, 256, 145, 389, 222, 301, 164, 377, 130, 288, 213, 349, 175)
+    assert len(sizes) == nb and sizes[16] < max(sizes)
+    gs = [(7 * j + 3) % 60 for j in range(nb)]
+    Rs = [tables.R64[g] for g in gs]
+    ds_h = []
+    for j, m in enumerate(sizes):                                        # copy j: 30 keypoints sit on points of its cloud
+        rows = np.concatenate([kidx_h[5:35], rs.permutation(4000)[:m - 30]])
+        ds_h.append((pts_h[rows[rs.permutation(m)]] @ np.asarray(Rs[j], dtype=np.float64).T).astype(np.float32))
+    for j in range(nb):
+        q = pts_h[kidx_h] @ np.asarray(Rs[j], dtype=np.float64).T
+        d2 = ((q[:, None, :] - ds_h[j].astype(np.float64)[None, :, :]) ** 2).sum(-1).min(1)
+        assert (np.sqrt(d2) < 0.9 * 2 * cell).any() and (d2 < 0.9 * 2 * cell).any(), j          # settled by the 5^3 block
+        assert (np.sqrt(d2) > 1.1 * 2 * cell).any() and (d2 > 1.1 * 2 * cell).any(), j          # must go to the fallback list
+    pts, kidx = cu(pts_h), cu(kidx_h)
+    ds = [cu(d) for d in ds_h]
+    ft = [cu(rs.randn(m, 32).astype(np.float32)) for m in sizes]
+    c.set_nn_grid(0)
+    ref = torch.zeros((K, 32, 60), dtype=torch.float32, device="cuda")
+    for j in range(nb):
+        q = c.rotate_select(pts, Rs[j], kidx)
+        _, idx = c.nn_search(q, ds[j], want_dist=False, squared=True)
+        c.group_scatter(ft[j], idx, g0 + j, ref)
+    c.set_nn_grid(cell)
+    out = torch.zeros_like(ref)
+    c.group_transfer_batch(pts, kidx, Rs, ds, ft, g0, out)
+    c.set_nn_grid(0)
+    assert torch.equal(out, ref)
+
+
 def test_grid_nn_equals_brute_force(hip, tables):
     """yoho_set_nn_grid changes the search, never the answer: both fp32 distance types and the f64 group gather, for a
     well-chosen cell, one that is far too small (most queries fall back to brute force) and a coarse one (long cell lists);

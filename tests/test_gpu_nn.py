@@ -3,8 +3,8 @@ against the oracle (tests/nn_ref.py: argmin of orc.pdist_l2 per row, orc.mutual_
 device path compared with another alone.  tests/test_nn_cpu.py shows on the CPU that these inputs reach what they are built for.
 
   * rounded ties: two targets whose D2 differ by 8e-6 relative and whose 'L2' distances sqrt(D2 + 1e-7) have equal bits, the larger
-    D2 at the lower index.  The reference answers the lower index under 'L2', the higher under 'SquareL2'.  yoho_nn_search (nn_kernel
-    below 2^20 pairs, nn32seg_kernel from there), yoho_knn_search(k = 1) and the four paths of yoho_mutual_nn.  Until nn_closer
+    D2 at the lower index.  The reference answers the lower index under 'L2', the higher under 'SquareL2'.  yoho_nn_search (nn32seg_kernel:
+    one row per thread below 2^20 pairs, two from there), yoho_knn_search(k = 1) and the four paths of yoho_mutual_nn.  Until nn_closer
     (csrc/nnmath.h) the brute-force kernels decided on D2 alone and returned the later index wherever one thread visited both
     targets (same segment, indices congruent mod 16): those cases failed for yoho_nn_search, for yoho_mutual_nn below 2^20 pairs,
     with the pre-filter off, and behind an overflowing candidate list;
@@ -23,7 +23,7 @@ import nn_ref as R  # noqa: E402
 
 orc = R.orc
 pytestmark = pytest.mark.gpu
-SMALL = ((5, 700), (33, 513))                                           # nn_kernel: below 2^20 pairs
+SMALL = ((5, 700), (33, 513))                                           # one-row nn32seg_kernel: below 2^20 pairs
 SEGMENTED = ((1024, 1024), (33, 32000), (4100, 257), (16384, 600))      # nn32seg_kernel; the last one has two tiles per segment
 
 
@@ -70,7 +70,7 @@ def n_cu():
 def tie_cases(D, Ns, Nt):
     """(what, src, tgt, lo, hi, one thread visits both) for every placement and scale of a shape"""
     segmented = Ns * Nt >= R.SEG_PAIRS
-    seg = R.seg_len(Ns, Nt, n_cu())[0] if segmented else None           # launch_nn32seg's segLen, restated (tests/nn_ref.py)
+    seg = R.seg_len(Ns, Nt, n_cu())[0] if segmented else None           # nn_segment_plan's segLen, restated (tests/nn_ref.py)
     src = R.tie_sources(D, Ns)
     for name, (lo, hi) in R.tie_placements(Nt, seg).items():
         for scale in R.TIE_SCALES:
@@ -120,7 +120,7 @@ MUTUAL_PATHS = {
 
 @pytest.mark.parametrize("path", list(MUTUAL_PATHS))
 def test_mutual_nn_rounded_ties(hip, path):
-    """ties in both directions (rows of a against b, rows of b against a) through nn_kernel, nn32seg_kernel, the pre-filter's exact
+    """ties in both directions (rows of a against b, rows of b against a) through nn32seg_kernel (one and two rows per thread), the pre-filter's exact
     candidates, and the fallback behind a candidate list that identical rows overflow: the match list is orc.mutual_match's and holds
     (query, lower index) of every cluster"""
     size, filler, pre = MUTUAL_PATHS[path]
@@ -156,7 +156,7 @@ def check_band(ctxs, key, a, b, cl, direction):
 def test_mutual_nn_band_cases(split_ctxs, size, direction):
     """adversarial queries at own rows 0, 127, 128 and the last one, their rivals in tile 0 of the other set and the true
     neighbours at its end (the last, ragged tile), so that rival and neighbour fall into different column splits unless there is one
-    split.  1025 x 1023 is one pair short of the pre-filter's threshold: nn_kernel answers, and has to give the same list."""
+    split.  1025 x 1023 is one pair short of the pre-filter's threshold: the one-row nn32seg_kernel answers, and has to give the same list."""
     a, b, cl = R.band_standard(*size, direction)
     assert (size[0] * size[1] >= R.SEG_PAIRS) == (size != (1025, 1023))
     n = check_band(split_ctxs, ("band", size, direction), a, b, cl, direction)

@@ -1,7 +1,7 @@
 """The inputs of tests/test_gpu_nn.py, checked where no device is needed: every generator of tests/nn_ref.py is shown on the oracle
 (and on emulations of what the device does before the exact distance decides) to reach the place it is built for.
 
-  * rounded ties: the oracle answers the lower index under 'L2' and the higher one under 'SquareL2'; the rule nn_kernel /
+  * rounded ties: the oracle answers the lower index under 'L2' and the higher one under 'SquareL2'; the rule
     nn32seg_kernel had answers the higher one under 'L2' wherever one thread visits both (same segment, congruent mod 16), the rule
     they have now (nn_closer) the oracle's;
   * the pre-filter's band: in every standard case the true neighbour's fp16 Gram score lies >= 0.35 of the shipped band above the row

@@ -6,10 +6,12 @@
     (utils/knn_search.py:68-106 written out with torch ops; its per-chunk copies to the host are left out, which favours it).
 
     python tools/time_nn.py [--repeats 5] [--window 0.3] [--out profiles/knn_search_timings.md]
-    python tools/time_nn.py --brute-only [--lib other/libyoho_hip.so]      # the brute-force searches alone (nn_kernel's family):
-                                                                           # yoho_nn_search 'L2' at 5000 x 5000 x 32 and x 3, mutual NN
-                                                                           # with the pre-filter off; --lib times another build of the
-                                                                           # library (a parent commit's) in a process of its own
+    python tools/time_nn.py --brute-only [--lib other/libyoho_hip.so]      # the brute-force searches alone (nn32seg_kernel's family):
+                                                                           # yoho_nn_search 'L2' at 5000 x 5000 and, below 2^20 pairs,
+                                                                           # at 1000 x 1000, x 32 and x 3; mutual NN with the pre-filter
+                                                                           # off; yoho_knn_search at k = 1, 4, 16; --lib times another
+                                                                           # build of the library (a parent commit's) in a process of
+                                                                           # its own
 
 One process, every variant warmed up, HIP events on the stream, a timed window repeats the call until it lasts `--window` seconds (a
 single call is tens of microseconds and would measure the launch), the variants alternate `--repeats` times; median and [min, max] of
@@ -103,7 +105,11 @@ def main():
         c.set_nn_prefilter(False)
         variants = [(("yoho_nn_search, 5000 x 5000 x 32, 'L2'", 1), lambda: c.nn_search(a, b, want_dist=True)),
                     (("yoho_nn_search, 5000 x 5000 x 3, 'L2'", 1), lambda: c.nn_search(q3, t3, want_dist=True)),
-                    (("mutual_nn, brute force, 5000 x 5000 x 32", "-"), lambda: c.mutual_nn(a, b))]
+                    (("mutual_nn, brute force, 5000 x 5000 x 32", "-"), lambda: c.mutual_nn(a, b)),
+                    (("yoho_nn_search, 1000 x 1000 x 32, 'L2'", 1), lambda: c.nn_search(a[:1000], b[:1000], want_dist=True)),
+                    (("yoho_nn_search, 1000 x 1000 x 3, 'L2'", 1), lambda: c.nn_search(q3[:1000], t3[:1000], want_dist=True))]
+        for k in (1, 4, 16):
+            variants.append((("yoho_knn_search, 5000 x 5000 x 32, 'L2'", k), lambda k=k: c.knn_search(a, b, k)))
         res = alternate(variants, args.repeats, args.window, probe)
         c.set_nn_prefilter(True)
         lines[0] += f"; library {hip._LIB_PATH if args.lib else 'of the tree'}"

@@ -17,8 +17,8 @@
 // unrolled: the body holds the insertion chain below, and 27 copies of a 31-step chain would not fit the instruction cache.  A lane
 // reads its own column only, so no barrier is needed.
 //
-// THE LIST.  The k best are packed keys (d2 bits << 32 | j), kept sorted ascending in CAP registers; d2 >= +0, so the order of the
-// integers is the contract's order of (d2, j) - matchf.hip's packing.  An empty place holds CL_EMPTY, all ones, above every key
+// THE LIST.  The k best are packed keys nn_key(d2 bits, j) (nnmath.h), kept sorted ascending in CAP registers; d2 >= +0, so the order of the
+// integers is the contract's order of (d2, j) - matchf.hip's packing.  An empty place holds NN_KEY_EMPTY, all ones, above every key
 // (a candidate's d2 is below the gate: finite, or below +inf).  A candidate is tested against the last place first; one that gets in
 // replaces it and sinks through a chain of CAP - 1 compare-exchanges whose indices are all compile-time constants, so the list stays
 // in registers (a register array indexed at run time goes to scratch).  k <= CAP: the list simply keeps CAP, the first k are the
@@ -38,7 +38,6 @@
 
 namespace yoho {
 
-constexpr u64 CL_EMPTY = ~0ull;
 constexpr unsigned CL_SEEN = 0xFFFFFFFFu;      // no slot: a slot is below 2^23
 constexpr int CL_SLAB = 2;                     // doubles per slab row
 
@@ -74,7 +73,7 @@ __device__ __forceinline__ int cl_walk(const RfGrid& g, const float (&q)[3], int
     }
     if constexpr (CAP > 0) {
 #pragma unroll
-        for (int m = 0; m < CAP; ++m) key[m] = CL_EMPTY;
+        for (int m = 0; m < CAP; ++m) key[m] = NN_KEY_EMPTY;
     }
     int n = 0;
 #pragma unroll 1
@@ -89,7 +88,7 @@ __device__ __forceinline__ int cl_walk(const RfGrid& g, const float (&q)[3], int
             const int j = __float_as_int(v.w);
             if (d2 < g.gate2 && j != self) {                              // false for a NaN / inf on either side
                 ++n;
-                if constexpr (CAP > 0) cl_insert<CAP>(key, ((u64)__float_as_uint(d2) << 32) | (u64)(unsigned)j);
+                if constexpr (CAP > 0) cl_insert<CAP>(key, nn_key(__float_as_uint(d2), (unsigned)j));
             }
         }
     }
@@ -110,9 +109,9 @@ __global__ __launch_bounds__(256) void cl_knn_kernel(RfGrid g, const float* __re
 #pragma unroll
         for (int m = 0; m < CAP; ++m) {
             if (m < k) {
-                const bool there = key[m] != CL_EMPTY;
-                if (idx) idx[(size_t)i * k + m] = there ? (int64_t)(unsigned)(key[m] & 0xFFFFFFFFull) : (int64_t)-1;
-                if (d2) d2[(size_t)i * k + m] = there ? __uint_as_float((unsigned)(key[m] >> 32)) : __builtin_inff();
+                const bool there = key[m] != NN_KEY_EMPTY;
+                if (idx) idx[(size_t)i * k + m] = there ? (int64_t)nn_key_index(key[m]) : (int64_t)-1;
+                if (d2) d2[(size_t)i * k + m] = there ? nn_key_dist(key[m]) : __builtin_inff();
             }
         }
     }
@@ -133,7 +132,7 @@ __global__ __launch_bounds__(256) void cl_stat_kernel(RfGrid g, const float* __r
         double s = 0.0;
 #pragma unroll
         for (int m = 0; m < CAP; ++m)
-            if (m < found) s = __dadd_rn(s, sqrt((double)__uint_as_float((unsigned)(key[m] >> 32))));
+            if (m < found) s = __dadd_rn(s, sqrt((double)nn_key_dist(key[m])));
         const bool valid = found >= min_found;                            // min_found >= 1: a non-finite point, count 0, is never valid
         const double mi = valid ? s / (double)found : __builtin_nan("");
         mws[i] = mi;

@@ -216,7 +216,7 @@ struct MfArgs {
     float* na2; float* nb2;              // squared norms
     _Float16* a16; _Float16* b16;        // the rows rounded to fp16 (RNE), 32 halfs each: the MFMA operands of both Gram passes
     unsigned* rowmin; unsigned* colmin;  // ordered-integer images of the minima of s (per a row) and t (per b row)
-    unsigned long long* keysA; unsigned long long* keysB;   // packed (distance bits << 32 | index) winners
+    unsigned long long* keysA; unsigned long long* keysB;   // packed (nn_key, nnmath.h) winners
     unsigned* maxn2;                     // [0] max |a_i|^2 bits, [1] max |b_j|^2 bits
     int* bad;                            // non-finite / out-of-range input: brute force instead
     int tilesPer;                        // 32-row tiles of the OTHER set per workgroup of the Gram passes
@@ -226,6 +226,10 @@ struct MfArgs {
 void mutual_prefilter_layout(Arena& ar, int Na, int Nb, MfArgs& p);
 // p: bound by mutual_prefilter_layout; p.keysA (Na) / p.keysB (Nb) receive the packed winners (the layout launch_mutual_compact<PACKED> reads)
 int launch_mutual_prefilter(MfArgs& p, const float* a, const float* b, int nCU, hipStream_t s, int nn_splits = 0);
+// the brute-force 1-NN search (match.hip).  keys == nullptr: the one-row kernel writes idx / dist (one segment, below 2^20 pairs).  Otherwise
+// the two-row kernel merges packed keys into keys (Ns words; init_keys: set to NN_KEY_EMPTY first) and runs only if *run_if != 0 (nullptr: always)
+int launch_nn32seg(const float* src, int Ns, const float* tgt, int Nt, int D, int dist_type, int nCU, unsigned long long* keys, bool init_keys,
+                   const int* run_if, int64_t* idx, float* dist, hipStream_t s);
 // scratch of the hash-grid searches (gridnn.hip): one open-addressing table of `cap` cells per copy, the chains of the target points
 // and the list of queries the grid could not resolve
 struct GridWs {

@@ -12,9 +12,14 @@
 // Every point outside that block is more than 2 cells away, so the result is final when the winner is closer than
 // 2 cells (with a 1e-4 relative slack that dwarfs every rounding involved).  Queries that fail the test (no point
 // nearby, hint too small) go to a list and are redone by brute force, one workgroup per query.
+//
+// Two sets of kernels use the grid: gn_* (one cloud, queries given; yoho_nn_search in 3-D and the f64 group gather) and gt_* (the copies
+// of a backbone pass in one launch, copy = blockIdx.y, the query rotated and the feature row written in the kernel).  They differ in
+// where the query comes from, which copy's table they address and where the winner goes; the insert (gn_insert), the 125-cell probe
+// (gn_probe) and the fallback scan (gn_scan) are written once, on the (distance, index) minimum of nntile.h.
 // Compiled with -ffp-contract=off like match.hip / estim.hip.
 #include "common.h"
-#include "nnmath.h"
+#include "nntile.h"
 
 namespace yoho {
 
@@ -39,9 +44,8 @@ __global__ void gn_clear_kernel(u64* keys, int* head, unsigned cap, int* ucount)
     if (i == 0) *ucount = 0;
 }
 
-__global__ void gn_build_kernel(const float* __restrict__ pts, int n, double inv_cell, u64* keys, int* head, int* next, unsigned mask) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+// point i of pts into the table: claim the cell's slot, push i on the cell's list
+__device__ __forceinline__ void gn_insert(const float* __restrict__ pts, int i, double inv_cell, u64* keys, int* head, int* next, unsigned mask) {
     const u64 key = gn_key(gn_cell((double)pts[3 * (size_t)i], inv_cell), gn_cell((double)pts[3 * (size_t)i + 1], inv_cell),
                            gn_cell((double)pts[3 * (size_t)i + 2], inv_cell));
     unsigned s = gn_slot(key, mask);
@@ -51,6 +55,12 @@ __global__ void gn_build_kernel(const float* __restrict__ pts, int n, double inv
         s = (s + 1) & mask;
     }
     next[i] = atomicExch(&head[s], i);             // list order is arbitrary; the query takes a (distance, index) minimum
+}
+
+__global__ void gn_build_kernel(const float* __restrict__ pts, int n, double inv_cell, u64* keys, int* head, int* next, unsigned mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    gn_insert(pts, i, inv_cell, keys, head, next, mask);
 }
 
 // MODE 0: f32 'SquareL2' (distance = squared), 1: f32 'L2', 2: f64 'L2' on keys rotated by Rg (group gather)
@@ -105,6 +115,42 @@ __device__ __forceinline__ void gn_store(const GnArgs& a, int q, typename GnMetr
     else { a.idx[q] = i; if (a.dist) a.dist[q] = (float)d; }
 }
 
+// One wave: the (distance, index) minimum over every point in the 5^3 cells around the query, left in every lane.  bi = 0x7FFFFFFF: no
+// point there (or all distances NaN).
+template <int MODE>
+__device__ __forceinline__ void gn_probe(const GnMetric<MODE>& m, double inv_cell, const u64* keys, const int* head, const int* next, unsigned mask,
+                                         const float* tgt, int lane, typename GnMetric<MODE>::dist_t& bd, int& bi) {
+    typedef typename GnMetric<MODE>::dist_t D;
+    const int cx = gn_cell(m.pos(0), inv_cell), cy = gn_cell(m.pos(1), inv_cell), cz = gn_cell(m.pos(2), inv_cell);
+    bd = gn_inf<D>();
+    bi = 0x7FFFFFFF;
+    for (int c = lane; c < 125; c += 64) {
+        const u64 key = gn_key(gn_clampi(cx + c % 5 - 2), gn_clampi(cy + (c / 5) % 5 - 2), gn_clampi(cz + c / 25 - 2));
+        unsigned s = gn_slot(key, mask);
+        int i = -1;
+        for (;;) {
+            const u64 k = keys[s];
+            if (k == key) { i = head[s]; break; }
+            if (k == GN_EMPTY) break;
+            s = (s + 1) & mask;
+        }
+        for (; i >= 0; i = next[i]) nn_take_min(bd, bi, m.eval(tgt + 3 * (size_t)i), i);
+    }
+    nn_wave_min(bd, bi);
+}
+
+// One workgroup: the brute-force (distance, index) minimum over all n points, left in rd[0] / ri[0] (256 entries each, in LDS).  All
+// distances NaN (NaN query): index 0, the brute-force kernels' answer.
+template <int MODE>
+__device__ __forceinline__ void gn_scan(const GnMetric<MODE>& m, const float* tgt, int n, typename GnMetric<MODE>::dist_t* rd, int* ri) {
+    typedef typename GnMetric<MODE>::dist_t D;
+    D bd = gn_inf<D>();
+    int bi = 0x7FFFFFFF;
+    for (int i = threadIdx.x; i < n; i += 256) nn_take_min(bd, bi, m.eval(tgt + 3 * (size_t)i), i);
+    nn_block_min(rd, ri, bd, bi);
+}
+__device__ __forceinline__ int gn_scan_index(const int* ri) { return ri[0] == 0x7FFFFFFF ? 0 : ri[0]; }
+
 template <int MODE>
 __global__ __launch_bounds__(256) void gn_query_kernel(GnArgs a) {
     typedef typename GnMetric<MODE>::dist_t D;
@@ -113,37 +159,16 @@ __global__ __launch_bounds__(256) void gn_query_kernel(GnArgs a) {
     if (q >= a.Ns) return;                                           // wave-uniform
     GnMetric<MODE> m;
     m.load(a.src, q, a.R);
-    const int cx = gn_cell(m.pos(0), a.inv_cell), cy = gn_cell(m.pos(1), a.inv_cell), cz = gn_cell(m.pos(2), a.inv_cell);
-    D bd = gn_inf<D>();
-    int bi = 0x7FFFFFFF;
-    for (int c = lane; c < 125; c += 64) {
-        const u64 key = gn_key(gn_clampi(cx + c % 5 - 2), gn_clampi(cy + (c / 5) % 5 - 2), gn_clampi(cz + c / 25 - 2));
-        unsigned s = gn_slot(key, a.mask);
-        int i = -1;
-        for (;;) {
-            const u64 k = a.keys[s];
-            if (k == key) { i = a.head[s]; break; }
-            if (k == GN_EMPTY) break;
-            s = (s + 1) & a.mask;
-        }
-        for (; i >= 0; i = a.next[i]) {
-            const D d = m.eval(a.tgt + 3 * (size_t)i);
-            if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const D od = __shfl_xor(bd, o);
-        const int oi = __shfl_xor(bi, o);
-        if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-    }
+    D bd;
+    int bi;
+    gn_probe<MODE>(m, a.inv_cell, a.keys, a.head, a.next, a.mask, a.tgt, lane, bd, bi);
     if (lane == 0) {
         if (bi != 0x7FFFFFFF && GnMetric<MODE>::resolved(bd, a.lim2)) gn_store<MODE>(a, q, bd, bi);
         else a.ulist[atomicAdd(a.ucount, 1)] = q;
     }
 }
 
-// brute force for the queries the grid could not settle: one workgroup per query, same arithmetic, (distance, index) minimum
+// brute force for the queries the grid could not settle: one workgroup per query, same arithmetic
 template <int MODE>
 __global__ __launch_bounds__(256) void gn_fallback_kernel(GnArgs a) {
     typedef typename GnMetric<MODE>::dist_t D;
@@ -154,25 +179,8 @@ __global__ __launch_bounds__(256) void gn_fallback_kernel(GnArgs a) {
         const int q = a.ulist[u];
         GnMetric<MODE> m;
         m.load(a.src, q, a.R);
-        D bd = gn_inf<D>();
-        int bi = 0x7FFFFFFF;
-        for (int i = threadIdx.x; i < a.Nt; i += 256) {
-            const D d = m.eval(a.tgt + 3 * (size_t)i);
-            if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
-        }
-        __syncthreads();
-        rd[threadIdx.x] = bd; ri[threadIdx.x] = bi;
-        __syncthreads();
-        for (int o = 128; o >= 1; o >>= 1) {
-            if (threadIdx.x < o) {
-                const D od = rd[threadIdx.x + o];
-                const int oi = ri[threadIdx.x + o];
-                if (od < rd[threadIdx.x] || (od == rd[threadIdx.x] && oi < ri[threadIdx.x])) { rd[threadIdx.x] = od; ri[threadIdx.x] = oi; }
-            }
-            __syncthreads();
-        }
-        // all distances NaN (NaN query): the brute-force kernels answer index 0
-        if (threadIdx.x == 0) gn_store<MODE>(a, q, rd[0], ri[0] == 0x7FFFFFFF ? 0 : ri[0]);
+        gn_scan<MODE>(m, a.tgt, a.Nt, rd, ri);
+        if (threadIdx.x == 0) gn_store<MODE>(a, q, rd[0], gn_scan_index(ri));
     }
 }
 
@@ -191,6 +199,12 @@ void grid_nn_layout(Arena& ar, int Ns, int Nt, GridWs& w) {
     w.ucount = ar.take<int>(1);
 }
 
+template <int MODE>
+static void gn_launch_search(const GnArgs& a, int nCU, hipStream_t s) {
+    hipLaunchKernelGGL(gn_query_kernel<MODE>, dim3((a.Ns + 3) / 4), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(gn_fallback_kernel<MODE>, dim3(nCU > 0 ? nCU : 256), dim3(256), 0, s, a);
+}
+
 int launch_grid_nn(int mode, const void* src, int Ns, const GnMat3* R, const float* tgt, int Nt, double cell, const GridWs& w, int64_t* idx, float* dist,
                    double* part_d, int* part_i, int nCU, hipStream_t s) {
     const unsigned cap = w.cap;
@@ -205,11 +219,10 @@ int launch_grid_nn(int mode, const void* src, int Ns, const GnMat3* R, const flo
     a.idx = idx; a.dist = dist; a.part_d = part_d; a.part_i = part_i;
     hipLaunchKernelGGL(gn_clear_kernel, dim3(cap / 256), dim3(256), 0, s, keys, head, cap, a.ucount);
     hipLaunchKernelGGL(gn_build_kernel, dim3((Nt + 255) / 256), dim3(256), 0, s, tgt, Nt, a.inv_cell, keys, head, next, a.mask);
-    const dim3 qg((Ns + 3) / 4), fg(nCU > 0 ? nCU : 256);
     switch (mode) {
-        case 0: hipLaunchKernelGGL(gn_query_kernel<0>, qg, dim3(256), 0, s, a); hipLaunchKernelGGL(gn_fallback_kernel<0>, fg, dim3(256), 0, s, a); break;
-        case 1: hipLaunchKernelGGL(gn_query_kernel<1>, qg, dim3(256), 0, s, a); hipLaunchKernelGGL(gn_fallback_kernel<1>, fg, dim3(256), 0, s, a); break;
-        default: hipLaunchKernelGGL(gn_query_kernel<2>, qg, dim3(256), 0, s, a); hipLaunchKernelGGL(gn_fallback_kernel<2>, fg, dim3(256), 0, s, a); break;
+        case 0: gn_launch_search<0>(a, nCU, s); break;
+        case 1: gn_launch_search<1>(a, nCU, s); break;
+        default: gn_launch_search<2>(a, nCU, s); break;
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -242,19 +255,7 @@ __global__ void gt_clear_kernel(u64* keys, int* head, size_t total, int* ucount,
 __global__ void gt_build_kernel(GtBatch a) {
     const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
     if (i >= a.m[b]) return;
-    const float* pts = a.ds[b];
-    u64* keys = a.keys + (size_t)b * a.cap;
-    int* head = a.head + (size_t)b * a.cap;
-    const unsigned mask = a.cap - 1;
-    const u64 key = gn_key(gn_cell((double)pts[3 * (size_t)i], a.inv_cell), gn_cell((double)pts[3 * (size_t)i + 1], a.inv_cell),
-                           gn_cell((double)pts[3 * (size_t)i + 2], a.inv_cell));
-    unsigned s = gn_slot(key, mask);
-    for (;;) {
-        const u64 old = atomicCAS(&keys[s], GN_EMPTY, key);
-        if (old == GN_EMPTY || old == key) break;
-        s = (s + 1) & mask;
-    }
-    a.next[(size_t)b * a.mmax + i] = atomicExch(&head[s], i);
+    gn_insert(a.ds[b], i, a.inv_cell, a.keys + (size_t)b * a.cap, a.head + (size_t)b * a.cap, a.next + (size_t)b * a.mmax, a.cap - 1);
 }
 
 // the rotated keypoint as the rotate kernel (spmaps.hip rotate_sel_kernel / point_of) forms it: f64 fma chain per coordinate, then float
@@ -278,35 +279,9 @@ __global__ __launch_bounds__(256) void gt_query_kernel(GtBatch a) {
     if (k >= a.K) return;                                            // wave-uniform
     GnMetric<0> m;
     gt_query_point(a, b, k, m.q);
-    const u64* keys = a.keys + (size_t)b * a.cap;
-    const int* head = a.head + (size_t)b * a.cap;
-    const int* next = a.next + (size_t)b * a.mmax;
-    const float* tgt = a.ds[b];
-    const unsigned mask = a.cap - 1;
-    const int cx = gn_cell(m.pos(0), a.inv_cell), cy = gn_cell(m.pos(1), a.inv_cell), cz = gn_cell(m.pos(2), a.inv_cell);
-    float bd = gn_inf<float>();
-    int bi = 0x7FFFFFFF;
-    for (int c = lane; c < 125; c += 64) {
-        const u64 key = gn_key(gn_clampi(cx + c % 5 - 2), gn_clampi(cy + (c / 5) % 5 - 2), gn_clampi(cz + c / 25 - 2));
-        unsigned s = gn_slot(key, mask);
-        int i = -1;
-        for (;;) {
-            const u64 kk = keys[s];
-            if (kk == key) { i = head[s]; break; }
-            if (kk == GN_EMPTY) break;
-            s = (s + 1) & mask;
-        }
-        for (; i >= 0; i = next[i]) {
-            const float d = m.eval(tgt + 3 * (size_t)i);
-            if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float od = __shfl_xor(bd, o);
-        const int oi = __shfl_xor(bi, o);
-        if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-    }
+    float bd;
+    int bi;
+    gn_probe<0>(m, a.inv_cell, a.keys + (size_t)b * a.cap, a.head + (size_t)b * a.cap, a.next + (size_t)b * a.mmax, a.cap - 1, a.ds[b], lane, bd, bi);
     if (bi != 0x7FFFFFFF && GnMetric<0>::resolved(bd, a.lim2)) gt_scatter(a, b, k, bi, lane);       // every lane holds the winner
     else if (lane == 0) a.ulist[(size_t)b * a.K + atomicAdd(a.ucount + b, 1)] = k;
 }
@@ -316,29 +291,12 @@ __global__ __launch_bounds__(256) void gt_fallback_kernel(GtBatch a) {
     __shared__ int ri[256];
     const int b = blockIdx.y;
     const int count = a.ucount[b];
-    const float* tgt = a.ds[b];
     for (int u = blockIdx.x; u < count; u += gridDim.x) {
         const int k = a.ulist[(size_t)b * a.K + u];
         GnMetric<0> m;
         gt_query_point(a, b, k, m.q);
-        float bd = gn_inf<float>();
-        int bi = 0x7FFFFFFF;
-        for (int i = threadIdx.x; i < a.m[b]; i += 256) {
-            const float d = m.eval(tgt + 3 * (size_t)i);
-            if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
-        }
-        __syncthreads();
-        rd[threadIdx.x] = bd; ri[threadIdx.x] = bi;
-        __syncthreads();
-        for (int o = 128; o >= 1; o >>= 1) {
-            if (threadIdx.x < o) {
-                const float od = rd[threadIdx.x + o];
-                const int oi = ri[threadIdx.x + o];
-                if (od < rd[threadIdx.x] || (od == rd[threadIdx.x] && oi < ri[threadIdx.x])) { rd[threadIdx.x] = od; ri[threadIdx.x] = oi; }
-            }
-            __syncthreads();
-        }
-        gt_scatter(a, b, k, ri[0] == 0x7FFFFFFF ? 0 : ri[0], threadIdx.x);       // all distances NaN: the brute-force kernels answer index 0
+        gn_scan<0>(m, a.ds[b], a.m[b], rd, ri);
+        gt_scatter(a, b, k, gn_scan_index(ri), threadIdx.x);
     }
 }
 

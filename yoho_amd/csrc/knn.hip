@@ -6,16 +6,17 @@
 // distance is match.hip's, bit for bit (nnmath.h: dist2_f32 in torch's CPU summation order, 'L2' = sqrt(D2 + 1e-7) correctly
 // rounded); this file is compiled with -ffp-contract=off like match.hip (yoho_amd/build.py).
 //
-// Shape: nn32seg_kernel's - a 256-row target tile in LDS, 16 lanes interleaved over the targets of a source row, two source rows per
-// thread (a target read from LDS feeds two distances), the targets cut into segments over blockIdx.y for large problems - with the
-// 16 lanes of a row ADJACENT in the wave (row group = threadIdx.x / 16, interleave = threadIdx.x % 16; the tile's rows are padded
-// to 36 floats so that the 16 different rows one ds_read_b128 fetches fall into 16 different bank quads).
+// Shape: nn32seg_kernel's, from the same pieces (nntile.h) - a 256-row target tile in LDS, 16 lanes interleaved over the targets of a
+// source row, two source rows per thread (a target read from LDS feeds two distances), the targets cut into segments over blockIdx.y
+// for large problems (nn_segment_plan) - with the 16 lanes of a row ADJACENT in the wave (row group = threadIdx.x / 16, interleave =
+// threadIdx.x % 16; the tile's rows are padded to 36 floats so that the 16 different rows one ds_read_b128 fetches fall into 16
+// different bank quads).
 //
 // The selection.  A sorted list of k keys per THREAD was considered and dropped on paper: a thread that has seen t of its targets
 // still inserts with probability k / t, a wave holds 128 (thread, row) lists, and one inserting lane makes the whole wave run the
 // insertion - with 128 k / t >= 1 for every t a segment reaches (t <= 45 at 5000 x 5000), the wave would run it at every step.
 // Here the 16 lanes of a row hold ONE sorted list between them: lane j keeps the j-th smallest key
-//     key = (bits of the fp32 distance as returned) << 32 | target index          (distances >= +0: integer order = float order)
+//     key = nn_key(bits of the fp32 distance as returned, target index)          (distances >= +0: integer order = float order)
 // so the list is always a top-16, whatever k is (no k buckets, one 64-bit register per row, nothing indexed dynamically: no scratch),
 // and a row inserts ~ k (1 + ln(N / k)) times per segment IN ALL.  A step computes 16 distances of the row; the lanes whose sum is
 // below the row's threshold T form their exact key, and the pending keys go in one by one: broadcast from the lowest pending lane,
@@ -28,7 +29,7 @@
 //     sqrt and its rounding are monotone, and s >= T = fl(fl(r r)(1 + 1e-6)) >= r^2 (1 + 8e-7) gives sqrt(s) >= r (1 + 3e-7) > r,
 //     i.e. a rounded distance >= r: rejected rightly.  The test is on the SUM, so it holds at every magnitude - D2 = 1e-15 and
 //     2e-15 both give s = 1e-7f, equal distance bits, a tie that the index decides (a relative test on D2 would call them clearly
-//     different; nn_kernel / nn32seg_kernel had one and now decide on the sums too: nn_closer, nnmath.h).  Sums in the band
+//     different; nn32seg_kernel had one and now decides on the sums too: nn_closer, nnmath.h).  Sums in the band
 //     [r^2, T) pay a square root for nothing; that is all.
 //   * NaN sums are folded to the one quiet NaN 0x7FC00000 (above +inf in integer order: NaN sorts last), so the keys stay totally
 //     ordered and a row of NaN / inf still gets k distinct in-range indices.
@@ -36,15 +37,13 @@
 // writes idx / dist.  Keys are exact, so the result cannot depend on the segment count; with one segment the search kernel writes
 // idx / dist itself.  No atomics.
 #include "common.h"
-#include "nnmath.h"
+#include "nntile.h"
 #include "yoho_knn.h"
 
 namespace yoho {
 
-constexpr int KNN_G = 16;        // lanes per source row = length of the distributed list
+constexpr int KNN_G = NN_SPLIT;  // lanes per source row = length of the distributed list
 constexpr int KNN_ROWS = 32;     // source rows per workgroup: 16 row groups x 2 rows per thread
-constexpr int KNN_TT = 256;      // target rows per LDS tile
-constexpr unsigned long long KNN_EMPTY = ~0ull;      // above every real key (indices are < 2^31)
 static_assert(YOHO_KNN_MAX == KNN_G, "the list is one key per lane of a row group");
 
 __device__ __forceinline__ unsigned long long knn_shfl64(unsigned long long v, int src) {
@@ -68,7 +67,7 @@ __device__ __forceinline__ void knn_insert(unsigned long long& ent, unsigned lon
     unsigned mask = (unsigned)(__ballot(pend) >> (lane & 48)) & 0xFFFFu;         // the pending lanes of this lane's group
     while (__any(mask != 0)) {
         unsigned long long cand = knn_shfl64(key, mask ? __ffs(mask) - 1 : 0);
-        if (!mask) cand = KNN_EMPTY;                                             // this group is done: EMPTY is below no entry
+        if (!mask) cand = NN_KEY_EMPTY;                                          // this group is done: EMPTY is below no entry
         const bool c = cand < ent;
         const unsigned long long prev = knn_shfl_up64(ent);
         const int cprev = __shfl_up((int)c, 1, KNN_G);
@@ -80,7 +79,7 @@ __device__ __forceinline__ void knn_insert(unsigned long long& ent, unsigned lon
 // the threshold on a candidate's bits (squared distance, or the sum D2 + 1e-7) below which it may enter a list whose k-th key is kth
 template <bool SQUARED>
 __device__ __forceinline__ unsigned knn_threshold(unsigned long long ent, int k) {
-    const unsigned r = __shfl((unsigned)(ent >> 32), k - 1, KNN_G);
+    const unsigned r = __shfl(__float_as_uint(nn_key_dist(ent)), k - 1, KNN_G);
     if (SQUARED || r >= 0x7F800000u) return r;                                   // inf, NaN, or fewer than k keys so far (0xFFFFFFFF)
     const float rf = __uint_as_float(r);
     return __float_as_uint(__fmul_rn(__fmul_rn(rf, rf), 1.0f + 1e-6f));
@@ -91,54 +90,34 @@ template <int D, bool SQUARED>
 __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ src, int Ns, const float* __restrict__ tgt, int Nt, int k, int segLen,
                                                   unsigned long long* __restrict__ keys, int64_t* __restrict__ idx, float* __restrict__ dist) {
     constexpr int LD = D % 4 == 0 ? D + 4 : D;       // tile row stride in floats
-    __shared__ __attribute__((aligned(16))) float tile[KNN_TT * LD];
+    __shared__ __attribute__((aligned(16))) float tile[NN_TT * LD];
     const int sp = threadIdx.x % KNN_G, g = threadIdx.x / KNN_G, lane = threadIdx.x & 63;
     const int row0 = blockIdx.x * KNN_ROWS + g, row1 = row0 + KNN_ROWS / 2;
     float a0[D], a1[D];
-    {
-        const int rc0 = row0 < Ns ? row0 : Ns - 1, rc1 = row1 < Ns ? row1 : Ns - 1;
-#pragma unroll
-        for (int f = 0; f < D; ++f) { a0[f] = src[(size_t)rc0 * D + f]; a1[f] = src[(size_t)rc1 * D + f]; }
-    }
-    unsigned long long e0 = KNN_EMPTY, e1 = KNN_EMPTY;
+    nn_load_row<D>(a0, a1, src, row0, row1, Ns);
+    unsigned long long e0 = NN_KEY_EMPTY, e1 = NN_KEY_EMPTY;
     unsigned T0 = 0xFFFFFFFFu, T1 = 0xFFFFFFFFu;
     const int tlo = blockIdx.y * segLen;
     const int thi = tlo + segLen < Nt ? tlo + segLen : Nt;
-    for (int t0 = tlo; t0 < thi; t0 += KNN_TT) {
-        const int nt = thi - t0 < KNN_TT ? thi - t0 : KNN_TT;
+    for (int t0 = tlo; t0 < thi; t0 += NN_TT) {
+        const int nt = thi - t0 < NN_TT ? thi - t0 : NN_TT;
         __syncthreads();
-        if constexpr (D % 4 == 0) {
-            const float4* g4 = reinterpret_cast<const float4*>(tgt + (size_t)t0 * D);      // rows of D floats from a 16-byte aligned base
-            float4* t4 = reinterpret_cast<float4*>(tile);
-            for (int i = threadIdx.x; i < nt * (D / 4); i += 256) t4[(i / (D / 4)) * (LD / 4) + i % (D / 4)] = g4[i];
-        } else {
-            for (int i = threadIdx.x; i < nt * D; i += 256) tile[i] = tgt[(size_t)t0 * D + i];
-        }
+        nn_stage_tile<D, LD>(tile, tgt, t0, nt, D % 4 == 0);                 // rows of D floats from a 16-byte aligned base
         __syncthreads();
         for (int tb = 0; tb < nt; tb += KNN_G) {
             const int tl = tb + sp;
             const bool valid = tl < nt;
-            const float* bp = tile + (valid ? tl : 0) * LD;
             float b[D];
-            if constexpr (D % 4 == 0) {
-#pragma unroll
-                for (int f = 0; f < D / 4; ++f) {
-                    const float4 v = reinterpret_cast<const float4*>(bp)[f];
-                    b[4 * f] = v.x; b[4 * f + 1] = v.y; b[4 * f + 2] = v.z; b[4 * f + 3] = v.w;
-                }
-            } else {
-#pragma unroll
-                for (int f = 0; f < D; ++f) b[f] = bp[f];
-            }
+            nn_tile_row<D, LD>(b, tile, valid ? tl : 0);
             float d0 = dist2_f32<D>(a0, b), d1 = dist2_f32<D>(a1, b);
             if (!SQUARED) { d0 = __fadd_rn(d0, 1e-7f); d1 = __fadd_rn(d1, 1e-7f); }      // dist_of_f32's sum; its square root below
             const unsigned u0 = knn_bits(d0), u1 = knn_bits(d1);
             const bool p0 = valid && u0 < T0, p1 = valid && u1 < T1;
             if (__any(p0 || p1)) {
                 const unsigned ti = (unsigned)(t0 + tl);
-                unsigned long long k0 = KNN_EMPTY, k1 = KNN_EMPTY;
-                if (p0) k0 = ((unsigned long long)(SQUARED ? u0 : knn_bits((float)sqrt((double)__uint_as_float(u0)))) << 32) | ti;
-                if (p1) k1 = ((unsigned long long)(SQUARED ? u1 : knn_bits((float)sqrt((double)__uint_as_float(u1)))) << 32) | ti;
+                unsigned long long k0 = NN_KEY_EMPTY, k1 = NN_KEY_EMPTY;
+                if (p0) k0 = nn_key(SQUARED ? u0 : knn_bits((float)sqrt((double)__uint_as_float(u0))), ti);
+                if (p1) k1 = nn_key(SQUARED ? u1 : knn_bits((float)sqrt((double)__uint_as_float(u1))), ti);
                 knn_insert(e0, k0, p0, sp, lane);
                 knn_insert(e1, k1, p1, sp, lane);
                 T0 = knn_threshold<SQUARED>(e0, k);
@@ -155,8 +134,8 @@ __global__ __launch_bounds__(256) void knn_kernel(const float* __restrict__ src,
             if (keys) {
                 keys[((size_t)row * gridDim.y + blockIdx.y) * k + sp] = e;
             } else {
-                idx[(size_t)row * k + sp] = (int64_t)(e & 0xFFFFFFFFull);
-                if (dist) dist[(size_t)row * k + sp] = __uint_as_float((unsigned)(e >> 32));
+                idx[(size_t)row * k + sp] = (int64_t)nn_key_index(e);
+                if (dist) dist[(size_t)row * k + sp] = nn_key_dist(e);
             }
         }
     }
@@ -168,9 +147,9 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const unsigned long long
     const int sp = threadIdx.x % KNN_G, g = threadIdx.x / KNN_G, lane = threadIdx.x & 63;
     const int row = blockIdx.x * (256 / KNN_G) + g;
     const unsigned long long* p = keys + (size_t)(row < Ns ? row : Ns - 1) * n;
-    unsigned long long e = KNN_EMPTY, kth = KNN_EMPTY;
+    unsigned long long e = NN_KEY_EMPTY, kth = NN_KEY_EMPTY;
     for (int tb = 0; tb < n; tb += KNN_G) {
-        const unsigned long long key = tb + sp < n ? p[tb + sp] : KNN_EMPTY;
+        const unsigned long long key = tb + sp < n ? p[tb + sp] : NN_KEY_EMPTY;
         const bool pend = key < kth;
         if (__any(pend)) {
             knn_insert(e, key, pend, sp, lane);
@@ -178,27 +157,9 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const unsigned long long
         }
     }
     if (row < Ns && sp < k) {
-        idx[(size_t)row * k + sp] = (int64_t)(e & 0xFFFFFFFFull);
-        if (dist) dist[(size_t)row * k + sp] = __uint_as_float((unsigned)(e >> 32));
+        idx[(size_t)row * k + sp] = (int64_t)nn_key_index(e);
+        if (dist) dist[(size_t)row * k + sp] = nn_key_dist(e);
     }
-}
-
-// segments of the targets: one below 2^20 pairs (a single launch, as yoho_nn_search's small kernel), else a few workgroups per CU
-static int knn_segments(int Ns, int Nt, int nCU, int* segLen) {
-    const int rb = (Ns + KNN_ROWS - 1) / KNN_ROWS;
-    int nseg = (size_t)Ns * Nt < (1u << 20) ? 1 : (4 * nCU + rb - 1) / rb;
-    const int maxseg = (Nt + 63) / 64;
-    nseg = nseg < 1 ? 1 : (nseg > maxseg ? maxseg : nseg);
-    int len = (Nt + nseg - 1) / nseg;
-    len = (len + 15) / 16 * 16;                     // tiles start at a multiple of 16 rows: 16-byte aligned for every D
-    *segLen = len;
-    return (Nt + len - 1) / len;
-}
-
-template <int D, bool SQUARED>
-static void knn_launch(dim3 grid, hipStream_t s, const float* src, int Ns, const float* tgt, int Nt, int k, int segLen, unsigned long long* keys,
-                       int64_t* idx, float* dist) {
-    hipLaunchKernelGGL((knn_kernel<D, SQUARED>), grid, dim3(256), 0, s, src, Ns, tgt, Nt, k, segLen, keys, idx, dist);
 }
 
 }  // namespace yoho
@@ -221,18 +182,18 @@ int yoho_knn_search(yoho_ctx* c, const float* src, int Ns, const float* tgt, int
     YOHO_NEED_ALIGNED("yoho_knn_search", 3, dist);
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    int segLen = 0;
-    const int nseg = knn_segments(Ns, Nt, c->nCU, &segLen);
+    // segments of the targets: one below 2^20 pairs (a single launch, as yoho_nn_search's one-row kernel), else a few workgroups per CU
+    const NnPlan plan = nn_segment_plan(Ns, Nt, KNN_ROWS, c->nCU, true);
+    const int nseg = plan.nseg;
     unsigned long long* keys = nullptr;
     if (nseg > 1) {
         int rc;
         if ((rc = bind_ws(c, s, [&](Arena& ar) { keys = ar.take<unsigned long long>((size_t)Ns * nseg * k); }))) return rc;
     }
     const dim3 grid((Ns + KNN_ROWS - 1) / KNN_ROWS, nseg);
-    if (D == 32 && !sq) knn_launch<32, false>(grid, s, src, Ns, tgt, Nt, k, segLen, keys, idx, dist);
-    else if (D == 32) knn_launch<32, true>(grid, s, src, Ns, tgt, Nt, k, segLen, keys, idx, dist);
-    else if (!sq) knn_launch<3, false>(grid, s, src, Ns, tgt, Nt, k, segLen, keys, idx, dist);
-    else knn_launch<3, true>(grid, s, src, Ns, tgt, Nt, k, segLen, keys, idx, dist);
+    nn_dispatch(D, sq, [&](auto d, auto q) {           // D was checked above
+        hipLaunchKernelGGL((knn_kernel<decltype(d)::value, decltype(q)::value>), grid, dim3(256), 0, s, src, Ns, tgt, Nt, k, plan.segLen, keys, idx, dist);
+    });
     HIPCHK(hipGetLastError());
     if (nseg > 1) {
         hipLaunchKernelGGL(knn_merge_kernel, dim3((Ns + 256 / KNN_G - 1) / (256 / KNN_G)), dim3(256), 0, s, keys, Ns, nseg * k, k, idx, dist);

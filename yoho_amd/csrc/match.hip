@@ -1,6 +1,6 @@
 // Brute-force nearest neighbour, mutual matching and the coarse-rotation index.
 //
-//   nn_kernel        modified_knn_matcher.pdist / find_nn_gpu   utils/knn_search.py:17-20,26-66
+//   nn32seg_kernel   modified_knn_matcher.pdist / find_nn_gpu   utils/knn_search.py:17-20,26-66
 //   mutual kernels   matcher_dual.match                         tests/matcher.py:37-48
 //   des2r_kernel     extractor_dr_index.Batch_Des2R_torch       tests/extractor.py:74-78
 //
@@ -9,99 +9,41 @@
 // round-to-nearest intrinsics (no FMA contraction) in the summation order torch's CPU reduction
 // uses for a contiguous 32-float row: 8 lane sums over x[l], x[8+l], x[16+l], x[24+l], lanes then
 // added 0..7 in sequence (pinned by tests/golden/pdist.npz).  The first minimum wins.
+// The tile, the packed key, the segment plan and the (distance, index) minimum are nntile.h's, shared with knn.hip and gridnn.hip.
 // This file is compiled with -ffp-contract=off (yoho_amd/build.py).
 #include "common.h"
-#include "nnmath.h"
+#include "nntile.h"
 
 namespace yoho {
 
-constexpr int NN_ROWS = 16;     // source rows per workgroup
-constexpr int NN_SPLIT = 16;    // target interleave per source row
-constexpr int NN_TT = 256;      // target rows per LDS tile
-
-// src (Ns,D) f32, tgt (Nt,D) f32 -> idx (Ns) int64, dist (Ns) f32 (optional)
-template <int D, bool SQUARED>
-__global__ __launch_bounds__(256) void nn_kernel(const float* __restrict__ src, int Ns, const float* __restrict__ tgt, int Nt,
-                                                 int64_t* __restrict__ idx, float* __restrict__ dist) {
-    __shared__ float tile[NN_TT * D];
-    __shared__ float rd[NN_ROWS * NN_SPLIT];
-    __shared__ int ri[NN_ROWS * NN_SPLIT];
-    const int r = threadIdx.x % NN_ROWS, sp = threadIdx.x / NN_ROWS;
-    const int row = blockIdx.x * NN_ROWS + r;
-    float a[D];
-    const int rowc = row < Ns ? row : Ns - 1;
-#pragma unroll
-    for (int k = 0; k < D; ++k) a[k] = src[(size_t)rowc * D + k];
-    // best holds the squared distance.  For the 'L2' form the reference compares sqrt(D2 + 1e-7) (first minimum): a later
-    // candidate wins only with a strictly smaller ROUNDED distance, which nn_closer (nnmath.h) decides on the sums D2 + 1e-7 -
-    // the correctly rounded sqrt (computed in f64) is evaluated only when the two sums are not proven 9e-7 apart.
-    auto dist_of = [](float d2) -> float { return dist_of_f32(d2); };
-    float best = __builtin_inff();
-    int besti = 0;
-    for (int t0 = 0; t0 < Nt; t0 += NN_TT) {
-        const int nt = Nt - t0 < NN_TT ? Nt - t0 : NN_TT;
-        __syncthreads();
-        for (int i = threadIdx.x; i < nt * D; i += 256) tile[i] = tgt[(size_t)t0 * D + i];
-        __syncthreads();
-        for (int t = sp; t < nt; t += NN_SPLIT) {
-            const float d2 = dist2_f32<D>(a, tile + t * D);
-            if (nn_closer<SQUARED>(d2, best)) { best = d2; besti = t0 + t; }
-        }
-    }
-    if (!SQUARED) best = dist_of(best);
-    rd[r * NN_SPLIT + sp] = best;
-    ri[r * NN_SPLIT + sp] = besti;
-    __syncthreads();
-    if (sp == 0 && row < Ns) {
-        float bd = rd[r * NN_SPLIT];
-        int bi = ri[r * NN_SPLIT];
-        for (int k = 1; k < NN_SPLIT; ++k) {
-            const float d = rd[r * NN_SPLIT + k];
-            const int i = ri[r * NN_SPLIT + k];
-            if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
-        }
-        idx[row] = bi;
-        if (dist) dist[row] = bd;
-    }
-}
-
-int launch_nn(const float* src, int Ns, const float* tgt, int Nt, int D, int dist_type, int64_t* idx, float* dist, hipStream_t s) {
-    const int grid = (Ns + NN_ROWS - 1) / NN_ROWS;
-    const bool sq = dist_type == YOHO_DIST_SQUARE_L2;
-    if (dist_type != YOHO_DIST_L2 && !sq) { set_error("yoho_nn_search: unknown dist_type %d", dist_type); return YOHO_EINVAL; }
-    if (D == 32 && !sq) hipLaunchKernelGGL((nn_kernel<32, false>), dim3(grid), dim3(256), 0, s, src, Ns, tgt, Nt, idx, dist);
-    else if (D == 32) hipLaunchKernelGGL((nn_kernel<32, true>), dim3(grid), dim3(256), 0, s, src, Ns, tgt, Nt, idx, dist);
-    else if (D == 3 && !sq) hipLaunchKernelGGL((nn_kernel<3, false>), dim3(grid), dim3(256), 0, s, src, Ns, tgt, Nt, idx, dist);
-    else if (D == 3) hipLaunchKernelGGL((nn_kernel<3, true>), dim3(grid), dim3(256), 0, s, src, Ns, tgt, Nt, idx, dist);
-    else { set_error("yoho_nn_search: D must be 32 or 3 (got %d)", D); return YOHO_EINVAL; }
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// D = 32, large problems: the same arithmetic, blocked for the LDS return path and for load balance.
+// One kernel, R source rows per thread (thread -> row r = threadIdx.x % 16 (+ 16 per further row), target lane sp = threadIdx.x / 16):
+//   R = 1, below 2^20 pairs: one segment, 16 rows per workgroup, idx / dist stored directly - one launch, no keys;
+//   R = 2, large problems: the same arithmetic, blocked for the LDS return path and for load balance.
 //   * a thread owns TWO source rows, so every target row read from LDS (8 x ds_read_b128) feeds two distance
-//     evaluations (the single-row kernel is bound by the LDS return bandwidth, not by its packed fp32 math);
-//   * the targets are cut into segments over blockIdx.y so that there are a few workgroups per CU whatever Ns is; the
-//     per-segment winners meet in a packed (distance bits << 32 | index) key with atomicMin — distances are
-//     non-negative, so the integer order is (distance, then lowest index) = the reference's first minimum.
+//     evaluations (with one row the kernel is bound by the LDS return bandwidth, not by its packed fp32 math);
+//   * the targets are cut into segments over blockIdx.y (nn_segment_plan) so that there are a few workgroups per CU whatever Ns
+//     is; the per-segment winners meet in a packed key (nn_key) with atomicMin, and nn_unpack_kernel writes idx / dist.
+// best holds the squared distance.  For the 'L2' form the reference compares sqrt(D2 + 1e-7) (first minimum): a later
+// candidate wins only with a strictly smaller ROUNDED distance, which nn_closer (nnmath.h) decides on the sums D2 + 1e-7 -
+// the correctly rounded sqrt (computed in f64) is evaluated only when the two sums are not proven 9e-7 apart.
 // ---------------------------------------------------------------------------------------------------------------
-template <int D, bool SQUARED>
+// src (Ns,D) f32, tgt (Nt,D) f32 -> R = 2: keys (Ns), initialised by the caller;  R = 1: idx (Ns) int64, dist (Ns) f32 (optional)
+template <int D, bool SQUARED, int R>
 __global__ __launch_bounds__(256) void nn32seg_kernel(const float* __restrict__ src, int Ns, const float* __restrict__ tgt, int Nt,
-                                                      unsigned long long* __restrict__ keys, int segLen, const int* __restrict__ run_if = nullptr) {
-    if (run_if && !*run_if) return;                  // fallback launch behind the MFMA pre-filter (matchf.hip): only if it declined
-    __shared__ __attribute__((aligned(16))) float tile[NN_TT * D];
-    __shared__ float rd[32 * NN_SPLIT];
-    __shared__ int ri[32 * NN_SPLIT];
-    const int r = threadIdx.x % 16, sp = threadIdx.x / 16;
-    const int row0 = blockIdx.x * 32 + r, row1 = row0 + 16;
-    float a0[D], a1[D];
-    {
-        const int rc0 = row0 < Ns ? row0 : Ns - 1, rc1 = row1 < Ns ? row1 : Ns - 1;
-#pragma unroll
-        for (int k = 0; k < D; ++k) { a0[k] = src[(size_t)rc0 * D + k]; a1[k] = src[(size_t)rc1 * D + k]; }
+                                                      unsigned long long* __restrict__ keys, int segLen, const int* __restrict__ run_if,
+                                                      int64_t* __restrict__ idx, float* __restrict__ dist) {
+    if constexpr (R == 2) {                          // fallback launch behind the MFMA pre-filter (matchf.hip): only if it declined.  Two rows
+        if (run_if && !*run_if) return;              // only: one row runs where a dependent load in front of the kernel's own shows
     }
-    auto dist_of = [](float d2) -> float { return dist_of_f32(d2); };
+    __shared__ __attribute__((aligned(16))) float tile[NN_TT * D];
+    __shared__ float rd[16 * R * NN_SPLIT];
+    __shared__ int ri[16 * R * NN_SPLIT];
+    const int r = threadIdx.x % 16, sp = threadIdx.x / 16;
+    const int row0 = blockIdx.x * (16 * R) + r;
+    float a0[D], a1[D];                              // a1, best1, bi1: the second row of a two-row thread
+    if constexpr (R == 2) nn_load_row<D>(a0, a1, src, row0, row0 + 16, Ns);
+    else nn_load_row<D>(a0, src, row0, Ns);
     float best0 = __builtin_inff(), best1 = __builtin_inff();
     int bi0 = 0, bi1 = 0;
     const int tlo = blockIdx.y * segLen;
@@ -109,47 +51,39 @@ __global__ __launch_bounds__(256) void nn32seg_kernel(const float* __restrict__ 
     for (int t0 = tlo; t0 < thi; t0 += NN_TT) {
         const int nt = thi - t0 < NN_TT ? thi - t0 : NN_TT;
         __syncthreads();
-        if ((nt * D) % 4 == 0) {
-            const float4* g4 = reinterpret_cast<const float4*>(tgt + (size_t)t0 * D);      // t0 is a multiple of 16 rows: 16-byte aligned
-            float4* t4 = reinterpret_cast<float4*>(tile);
-            for (int i = threadIdx.x; i < nt * D / 4; i += 256) t4[i] = g4[i];
-        } else {
-            for (int i = threadIdx.x; i < nt * D; i += 256) tile[i] = tgt[(size_t)t0 * D + i];
-        }
+        // t0 is a multiple of 16 rows.  One row per thread stages with scalar loads: the compiler keeps eight of them in flight where it
+        // issues one float4 at a time, and a grid of a few dozen workgroups has nothing to hide that latency behind (profiles/nn_family_refactor.md)
+        nn_stage_tile<D, D>(tile, tgt, t0, nt, R == 2 && (nt * D) % 4 == 0);
         __syncthreads();
         for (int t = sp; t < nt; t += NN_SPLIT) {
             float b[D];
-            if constexpr (D % 4 == 0) {
-#pragma unroll
-                for (int k = 0; k < D / 4; ++k) {
-                    const float4 v = reinterpret_cast<const float4*>(tile + t * D)[k];
-                    b[4 * k] = v.x; b[4 * k + 1] = v.y; b[4 * k + 2] = v.z; b[4 * k + 3] = v.w;
-                }
+            nn_tile_row<D, D>(b, tile, t);
+            if constexpr (R == 2) {
+                const float d0 = dist2_f32<D>(a0, b), d1 = dist2_f32<D>(a1, b);
+                if (nn_closer<SQUARED>(d0, best0)) { best0 = d0; bi0 = t0 + t; }
+                if (nn_closer<SQUARED>(d1, best1)) { best1 = d1; bi1 = t0 + t; }
             } else {
-#pragma unroll
-                for (int k = 0; k < D; ++k) b[k] = tile[t * D + k];
+                const float d0 = dist2_f32<D>(a0, b);
+                if (nn_closer<SQUARED>(d0, best0)) { best0 = d0; bi0 = t0 + t; }
             }
-            const float d0 = dist2_f32<D>(a0, b), d1 = dist2_f32<D>(a1, b);
-            if (nn_closer<SQUARED>(d0, best0)) { best0 = d0; bi0 = t0 + t; }
-            if (nn_closer<SQUARED>(d1, best1)) { best1 = d1; bi1 = t0 + t; }
         }
     }
-    if (!SQUARED) { best0 = dist_of(best0); best1 = dist_of(best1); }
+    if (!SQUARED) { best0 = dist_of_f32(best0); best1 = dist_of_f32(best1); }           // (best1 is dead code with one row)
     rd[r * NN_SPLIT + sp] = best0; ri[r * NN_SPLIT + sp] = bi0;
-    rd[(r + 16) * NN_SPLIT + sp] = best1; ri[(r + 16) * NN_SPLIT + sp] = bi1;
+    if constexpr (R == 2) { rd[(r + 16) * NN_SPLIT + sp] = best1; ri[(r + 16) * NN_SPLIT + sp] = bi1; }
     __syncthreads();
-    if (threadIdx.x < 32) {
-        const int rr = threadIdx.x, row = blockIdx.x * 32 + rr;
+    if (threadIdx.x < 16 * R) {
+        const int rr = threadIdx.x, row = blockIdx.x * (16 * R) + rr;
         if (row < Ns && tlo < thi) {
-            float bd = rd[rr * NN_SPLIT];
-            int bi = ri[rr * NN_SPLIT];
-            for (int k = 1; k < NN_SPLIT; ++k) {
-                const float d = rd[rr * NN_SPLIT + k];
-                const int i = ri[rr * NN_SPLIT + k];
-                if (d < bd || (d == bd && i < bi)) { bd = d; bi = i; }
+            float bd;
+            int bi;
+            nn_row_winner(rd, ri, rr, bd, bi);
+            if constexpr (R == 1) {
+                idx[row] = bi;
+                if (dist) dist[row] = bd;
+            } else {
+                atomicMin(keys + row, nn_key(__float_as_uint(bd), (unsigned)bi));
             }
-            const unsigned long long key = ((unsigned long long)__float_as_uint(bd) << 32) | (unsigned)bi;
-            atomicMin(keys + row, key);
         }
     }
 }
@@ -159,39 +93,24 @@ __global__ __launch_bounds__(256) void nn_unpack_kernel(const unsigned long long
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Ns) return;
     const unsigned long long k = keys[i];
-    idx[i] = (int64_t)(k & 0xFFFFFFFFull);
-    if (dist) dist[i] = __uint_as_float((unsigned)(k >> 32));
+    idx[i] = (int64_t)nn_key_index(k);
+    if (dist) dist[i] = nn_key_dist(k);
 }
 
-// the same search into keys that are ALREADY initialised, run only if *run_if is non-zero (D = 32, 'L2' distance)
-int launch_nn32seg_if(const float* src, int Ns, const float* tgt, int Nt, unsigned long long* keys, int nCU, const int* run_if, hipStream_t s) {
-    const int rb = (Ns + 31) / 32;
-    int nseg = (4 * nCU + rb - 1) / rb;
-    const int maxseg = (Nt + 63) / 64;
-    nseg = nseg < 1 ? 1 : (nseg > maxseg ? maxseg : nseg);
-    int segLen = (Nt + nseg - 1) / nseg;
-    segLen = (segLen + 15) / 16 * 16;
-    nseg = (Nt + segLen - 1) / segLen;
-    hipLaunchKernelGGL((nn32seg_kernel<32, false>), dim3(rb, nseg), dim3(256), 0, s, src, Ns, tgt, Nt, keys, segLen, run_if);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-// keys must hold Ns words; they are (re)initialised here
-int launch_nn32seg(const float* src, int Ns, const float* tgt, int Nt, bool squared, unsigned long long* keys, int nCU, hipStream_t s,
-                   int D = 32) {
-    const int rb = (Ns + 31) / 32;
-    int nseg = (4 * nCU + rb - 1) / rb;
-    const int maxseg = (Nt + 63) / 64;
-    nseg = nseg < 1 ? 1 : (nseg > maxseg ? maxseg : nseg);
-    int segLen = (Nt + nseg - 1) / nseg;
-    segLen = (segLen + 15) / 16 * 16;
-    nseg = (Nt + segLen - 1) / segLen;
-    HIPCHK(hipMemsetAsync(keys, 0xFF, sizeof(unsigned long long) * (size_t)Ns, s));
-    if (D == 3 && squared) hipLaunchKernelGGL((nn32seg_kernel<3, true>), dim3(rb, nseg), dim3(256), 0, s, src, Ns, tgt, Nt, keys, segLen, (const int*)nullptr);
-    else if (D == 3) hipLaunchKernelGGL((nn32seg_kernel<3, false>), dim3(rb, nseg), dim3(256), 0, s, src, Ns, tgt, Nt, keys, segLen, (const int*)nullptr);
-    else if (squared) hipLaunchKernelGGL((nn32seg_kernel<32, true>), dim3(rb, nseg), dim3(256), 0, s, src, Ns, tgt, Nt, keys, segLen, (const int*)nullptr);
-    else hipLaunchKernelGGL((nn32seg_kernel<32, false>), dim3(rb, nseg), dim3(256), 0, s, src, Ns, tgt, Nt, keys, segLen, (const int*)nullptr);
+// the one launcher of the brute-force search (arguments: common.h); the callers take the one-row kernel below 2^20 pairs
+int launch_nn32seg(const float* src, int Ns, const float* tgt, int Nt, int D, int dist_type, int nCU, unsigned long long* keys, bool init_keys,
+                   const int* run_if, int64_t* idx, float* dist, hipStream_t s) {
+    const bool sq = dist_type == YOHO_DIST_SQUARE_L2;
+    if (dist_type != YOHO_DIST_L2 && !sq) { set_error("yoho_nn_search: unknown dist_type %d", dist_type); return YOHO_EINVAL; }
+    if (D != 32 && D != 3) { set_error("yoho_nn_search: D must be 32 or 3 (got %d)", D); return YOHO_EINVAL; }
+    const int rows = keys ? 32 : 16;
+    const NnPlan plan = keys ? nn_segment_plan(Ns, Nt, rows, nCU, false) : NnPlan{Nt, 1};
+    const dim3 grid((Ns + rows - 1) / rows, plan.nseg);
+    if (keys && init_keys) HIPCHK(hipMemsetAsync(keys, 0xFF, sizeof(unsigned long long) * (size_t)Ns, s));      // NN_KEY_EMPTY
+    nn_dispatch(D, sq, [&](auto d, auto q) {
+        if (keys) hipLaunchKernelGGL((nn32seg_kernel<decltype(d)::value, decltype(q)::value, 2>), grid, dim3(256), 0, s, src, Ns, tgt, Nt, keys, plan.segLen, run_if, idx, dist);
+        else hipLaunchKernelGGL((nn32seg_kernel<decltype(d)::value, decltype(q)::value, 1>), grid, dim3(256), 0, s, src, Ns, tgt, Nt, keys, plan.segLen, run_if, idx, dist);
+    });
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -203,7 +122,7 @@ int launch_nn_unpack(const unsigned long long* keys, int Ns, int64_t* idx, float
 }
 
 // keep i with back[fwd[i]] == i, ascending i (tests/matcher.py:42-47).  Single workgroup scan.
-// PACKED: fwd / back hold (distance bits << 32 | index) keys of the segmented search.
+// PACKED: fwd / back hold the packed keys (nn_key) of the segmented search.
 template <bool PACKED>
 __global__ __launch_bounds__(1024) void mutual_compact_kernel(const int64_t* __restrict__ fwd, const int64_t* __restrict__ back,
                                                               int Na, int64_t* __restrict__ pairs, int* __restrict__ M_out) {
@@ -217,8 +136,8 @@ __global__ __launch_bounds__(1024) void mutual_compact_kernel(const int64_t* __r
         bool keep = false;
         int64_t j = 0;
         if (i < Na) {
-            j = PACKED ? (fwd[i] & 0xFFFFFFFFll) : fwd[i];
-            const int64_t bk = PACKED ? (back[j] & 0xFFFFFFFFll) : back[j];
+            j = PACKED ? (int64_t)nn_key_index((unsigned long long)fwd[i]) : fwd[i];
+            const int64_t bk = PACKED ? (int64_t)nn_key_index((unsigned long long)back[j]) : back[j];
             keep = bk == (int64_t)i;
         }
         const unsigned long long m = __ballot(keep);
@@ -361,10 +280,10 @@ int yoho_nn_search(yoho_ctx* c, const float* src, int Ns, const float* tgt, int 
         int rc;
         unsigned long long* keys = nullptr;
         if ((rc = bind_ws(c, (hipStream_t)stream, [&](Arena& ar) { keys = ar.take<unsigned long long>((size_t)Ns); }))) return rc;
-        if ((rc = launch_nn32seg(src, Ns, tgt, Nt, dist_type == YOHO_DIST_SQUARE_L2, keys, c->nCU, (hipStream_t)stream, D))) return rc;
+        if ((rc = launch_nn32seg(src, Ns, tgt, Nt, D, dist_type, c->nCU, keys, true, nullptr, nullptr, nullptr, (hipStream_t)stream))) return rc;
         return launch_nn_unpack(keys, Ns, idx, dist, (hipStream_t)stream);
     }
-    return launch_nn(src, Ns, tgt, Nt, D, dist_type, idx, dist, (hipStream_t)stream);
+    return launch_nn32seg(src, Ns, tgt, Nt, D, dist_type, c->nCU, nullptr, false, nullptr, idx, dist, (hipStream_t)stream);
 }
 
 int yoho_mutual_nn(yoho_ctx* c, const float* a, int Na, const float* b, int Nb, int64_t* pairs, int* M_out, void* stream) {
@@ -385,12 +304,12 @@ int yoho_mutual_nn(yoho_ctx* c, const float* a, int Na, const float* b, int Nb, 
     if ((rc = bind_ws(c, s, [&](Arena& ar) { fwd = ar.take<int64_t>((size_t)Na); back = ar.take<int64_t>((size_t)Nb); }))) return rc;
     if ((size_t)Na * Nb >= (1u << 20)) {
         // segmented search: the workspace words are the packed keys, the compaction reads the index half
-        if ((rc = launch_nn32seg(a, Na, b, Nb, false, (unsigned long long*)fwd, c->nCU, s))) return rc;
-        if ((rc = launch_nn32seg(b, Nb, a, Na, false, (unsigned long long*)back, c->nCU, s))) return rc;
+        if ((rc = launch_nn32seg(a, Na, b, Nb, 32, YOHO_DIST_L2, c->nCU, (unsigned long long*)fwd, true, nullptr, nullptr, nullptr, s))) return rc;
+        if ((rc = launch_nn32seg(b, Nb, a, Na, 32, YOHO_DIST_L2, c->nCU, (unsigned long long*)back, true, nullptr, nullptr, nullptr, s))) return rc;
         return launch_mutual_compact(fwd, back, Na, pairs, M_out, s, true);
     }
-    if ((rc = launch_nn(a, Na, b, Nb, 32, YOHO_DIST_L2, fwd, nullptr, s))) return rc;     // NN of every a-row in b  (KNN(feats1, feats0))
-    if ((rc = launch_nn(b, Nb, a, Na, 32, YOHO_DIST_L2, back, nullptr, s))) return rc;    // NN of every b-row in a  (KNN(feats0, feats1))
+    if ((rc = launch_nn32seg(a, Na, b, Nb, 32, YOHO_DIST_L2, c->nCU, nullptr, false, nullptr, fwd, nullptr, s))) return rc;     // NN of every a-row in b  (KNN(feats1, feats0))
+    if ((rc = launch_nn32seg(b, Nb, a, Na, 32, YOHO_DIST_L2, c->nCU, nullptr, false, nullptr, back, nullptr, s))) return rc;    // NN of every b-row in a  (KNN(feats0, feats1))
     return launch_mutual_compact(fwd, back, Na, pairs, M_out, s);
 }
 

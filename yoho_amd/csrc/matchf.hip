@@ -9,7 +9,7 @@
 //            term that is constant along the search): a workgroup serves ONE direction, owns 128 rows of its set and streams the
 //            other set past them, so a minimum is a register until the end (one ordered-integer atomicMin per row and workgroup);
 //   pass 2   every (i, j) whose score is within a PROVEN error band of its row (column) minimum is a candidate: its exact distance
-//            is evaluated with dist2_f32 / dist_of_f32 and merged as the packed key (distance bits << 32 | index) the brute-force
+//            is evaluated with dist2_f32 / dist_of_f32 and merged as the packed key (nn_key, nnmath.h) the brute-force
 //            path uses, so ties go to the lowest index as there.
 // Band.  With u16 = 2^-11 (fp16 rounding), |G~ - G| <= (2 u16 + u16^2 + 32 * 2^-24) |a_i||b_j| <= 1.0e-3 |a_i||b_j|, the fp32 norms
 // are off by <= 33 * 2^-24 |b_j|^2, the explicit-difference sums by <= 40 * 2^-24 (|a_i| + |b_j|)^2, fp16 subnormals add at most
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void mf_norms_kernel(MfArgs p) {
         }
         (isa ? p.na2 : p.nb2)[r] = s;
         (isa ? p.rowmin : p.colmin)[r] = 0xFFFFFFFFu;
-        (isa ? p.keysA : p.keysB)[r] = ~0ull;
+        (isa ? p.keysA : p.keysB)[r] = NN_KEY_EMPTY;
     }
     const bool bad = live && (!(s <= 1e30f) || !(m <= 6.0e4f));          // NaN / inf / beyond the fp16 range
     if (__ballot(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(p.bad, 1);
@@ -82,7 +82,7 @@ __device__ __forceinline__ float band_of(float n2, float m2) {
     return 4.5e-3f * mine * other + 2e-5f * sum * sum + 4e-6f * sum + 1e-30f;
 }
 
-// exact distances of the candidates of pass 2, one thread per pair, merged as packed keys (distance bits << 32 | index) like the
+// exact distances of the candidates of pass 2, one thread per pair, merged as packed keys (nn_key) like the
 // brute-force kernels do.  In pass 2 a candidate used to be evaluated on the spot: one ~150-instruction divergent call per
 // (column slab, register) slot with any candidate in the wave - that was most of the pass.
 __global__ __launch_bounds__(256) void mf_exact_kernel(MfArgs p) {
@@ -99,9 +99,9 @@ __global__ __launch_bounds__(256) void mf_exact_kernel(MfArgs p) {
             bv[4 * k] = y.x; bv[4 * k + 1] = y.y; bv[4 * k + 2] = y.z; bv[4 * k + 3] = y.w;
         }
         // (a - b)^2 and (b - a)^2 are the same floats, so one evaluation serves both search directions
-        const unsigned long long d = (unsigned long long)__float_as_uint(dist_of_f32(dist2_f32<32>(av, bv))) << 32;
-        if (e & 2ull) atomicMin(p.keysA + i, d | (unsigned)j);
-        if (e & 1ull) atomicMin(p.keysB + j, d | (unsigned)i);
+        const unsigned d = __float_as_uint(dist_of_f32(dist2_f32<32>(av, bv)));
+        if (e & 2ull) atomicMin(p.keysA + i, nn_key(d, (unsigned)j));
+        if (e & 1ull) atomicMin(p.keysB + j, nn_key(d, (unsigned)i));
     }
 }
 
@@ -248,8 +248,6 @@ __global__ __launch_bounds__(256) void mf_gram_kernel(MfArgs p) {
     }
 }
 
-int launch_nn32seg_if(const float* src, int Ns, const float* tgt, int Nt, unsigned long long* keys, int nCU, const int* run_if, hipStream_t s);
-
 void mutual_prefilter_layout(Arena& ar, int Na, int Nb, MfArgs& p) {
     p.Na = Na; p.Nb = Nb;
     p.keysA = ar.take<unsigned long long>((size_t)Na);
@@ -286,8 +284,8 @@ int launch_mutual_prefilter(MfArgs& p, const float* a, const float* b, int nCU, 
     HIPCHK(hipGetLastError());
     // inputs the pre-filter cannot take: the brute-force kernels run (they return at once otherwise)
     int rc;
-    if ((rc = launch_nn32seg_if(a, Na, b, Nb, p.keysA, nCU, p.bad, s))) return rc;
-    return launch_nn32seg_if(b, Nb, a, Na, p.keysB, nCU, p.bad, s);
+    if ((rc = launch_nn32seg(a, Na, b, Nb, 32, YOHO_DIST_L2, nCU, p.keysA, false, p.bad, nullptr, nullptr, s))) return rc;
+    return launch_nn32seg(b, Nb, a, Na, 32, YOHO_DIST_L2, nCU, p.keysB, false, p.bad, nullptr, nullptr, s);
 }
 
 }  // namespace yoho

@@ -1,5 +1,5 @@
-// Distance arithmetic shared by the brute-force and the grid nearest-neighbour kernels (match.hip, estim.hip,
-// gridnn.hip): explicit round-to-nearest intrinsics in the summation order the reference's CPU reduction uses
+// Distance arithmetic shared by the brute-force and the grid nearest-neighbour kernels (match.hip, knn.hip, estim.hip,
+// gridnn.hip; the tile, key and minimum they share: nntile.h): explicit round-to-nearest intrinsics in the summation order the reference's CPU reduction uses
 // (pinned by tests/golden/pdist.npz); the translation units that include this are built with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -38,7 +38,7 @@ __device__ __forceinline__ float dist2_f32(const float* a, const float* b) {
 // pdist 'L2': sqrt(D2 + 1e-7) as torch evaluates it on fp32 (utils/knn_search.py:17-20)
 __device__ __forceinline__ float dist_of_f32(float d2) { return (float)sqrt((double)__fadd_rn(d2, 1e-7f)); }
 
-// The first-minimum rule of the brute-force searches (nn_kernel, nn32seg_kernel): does a LATER target with squared distance d2
+// The first-minimum rule of the brute-force searches (nn32seg_kernel): does a LATER target with squared distance d2
 // replace the best so far (squared distance `best`)?  SquareL2: d2 < best.  L2: only a strictly smaller ROUNDED distance does, and
 // what decides are the sums s = fl(d2 + e), sb = fl(best + e), e = 1e-7f, that the square root is taken of, as in knn.hip - a
 // relative test on d2 itself (these kernels had `d2 < best (1 - 1e-6)`) is wrong once d2 is small against e: D2 = 1e-9 and
@@ -59,6 +59,14 @@ __device__ __forceinline__ bool nn_closer(float d2, float best) {
     if (d2 < fmaf(best, 1.0f - 1e-6f, -1.1e-13f)) return true;
     return dist_of_f32(d2) < dist_of_f32(best);
 }
+
+// The packed key of the searches (match.hip, matchf.hip, knn.hip, clean.hip): (bits of a distance >= +0) << 32 | index.  Distances are
+// non-negative, so the order of the integers is the order of (distance, then lowest index) = the reference's first minimum; atomicMin and
+// sorted lists work on the key alone.
+constexpr unsigned long long NN_KEY_EMPTY = ~0ull;           // above every real key (indices are < 2^31); a memset of 0xFF bytes
+__device__ __forceinline__ unsigned long long nn_key(unsigned dist_bits, unsigned index) { return ((unsigned long long)dist_bits << 32) | index; }
+__device__ __forceinline__ float nn_key_dist(unsigned long long key) { return __uint_as_float((unsigned)(key >> 32)); }
+__device__ __forceinline__ unsigned nn_key_index(unsigned long long key) { return (unsigned)(key & 0xFFFFFFFFull); }
 
 // one coordinate of keys @ Rg^T in f64 (YOHO_testset.py:157) and the f64 squared distance to a widened f32 point
 struct GnMat3 { double m[9]; };
