@@ -7,10 +7,13 @@ two fragments overlap.  The two filters every point-cloud library has, on the ex
     statistical(ctx, pts, k=16, std_ratio=2.0, max_dist=0.1)      mean distance to the k nearest inside max_dist, keep <= mean + 2 sigma
     radius(ctx, pts, 0.05, 8)                                     keep the points with >= 8 others inside 0.05
     sel, kept = clean_cloud(ctx, pc_d, max_dist=0.1)              either of them on an (n,3) f64 cloud
+    clean_cloud(ctx, pc_d, method="cluster", eps=0.1, min_size=100)   strays that come in clumps: yoho_amd.cluster.keep_large
 
 Opt-in consumers: keypoints.select(..., clean={...}), yoho_extractor(..., keypoint_clean={...}), fuse.write_scene_cloud(..., clean={...}).
 """
 import torch
+
+from . import cluster
 
 
 def _result(keep, mean_dist, stats, **more):
@@ -42,7 +45,17 @@ def radius(ctx, pts_f32, radius, min_nbrs):
     return _result(count >= int(min_nbrs), None, None, count=count)
 
 
-METHODS = {"statistical": statistical, "radius": radius}
+METHODS = {"statistical": statistical, "radius": radius, "cluster": cluster.keep_large}
+# the argument that carries a method's radius: what the consumers default to 4 voxels
+RADIUS_KEY = {"statistical": "max_dist", "radius": "radius", "cluster": "eps"}
+
+
+def method_of(clean):
+    """a consumer's clean dict -> (method, its radius argument's name): the optional "method" key, "statistical" when absent"""
+    method = clean.get("method", "statistical")
+    if method not in METHODS:
+        raise ValueError(f"clean: method must be one of {sorted(METHODS)}, got {method!r}")
+    return method, RADIUS_KEY[method]
 
 
 def clean_cloud(ctx, pc_d, method="statistical", **kw):

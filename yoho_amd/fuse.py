@@ -119,13 +119,18 @@ def filter_rows(out, sel):
 
 def clean_fused(ctx, out, clean):
     """the fused result (host arrays) without the rows yoho_amd.clean.statistical drops from its points.  clean: a dict of that function's
-    keyword arguments; max_dist has to be among them (a fused cloud's spacing is its voxel's: 4 voxels is the usual choice)."""
+    keyword arguments; max_dist has to be among them (a fused cloud's spacing is its voxel's: 4 voxels is the usual choice).  An
+    optional "method" key names another filter of yoho_amd.clean.METHODS ("cluster": yoho_amd.cluster.keep_large, with its eps); the
+    other keys are then that filter's arguments."""
     import torch
     from . import clean as CL
     from . import hip
     ctx = hip.get_context() if ctx is None else ctx
     pts = torch.from_numpy(np.ascontiguousarray(out["pts"], dtype=f32)).cuda()
-    return filter_rows(out, CL.statistical(ctx, pts, **dict(clean))["sel"].cpu().numpy())
+    kw = dict(clean)
+    method = CL.method_of(kw)[0]
+    kw.pop("method", None)
+    return filter_rows(out, CL.METHODS[method](ctx, pts, **kw)["sel"].cpu().numpy())
 
 
 def _device_fuse(ctx):
@@ -145,7 +150,8 @@ def write_scene_cloud(cfg, dataset, yoho_sign='YOHO_O_MW', voxel=0.025, min_frag
     pose per fragment, nan for an unreached one) and the dataset's clouds, fuses them and writes scene.ply beside the log: the mean point
     of every voxel that >= min_count points of >= min_frags fragments fed, with both counts.
     fuse(clouds, poses, voxel, min_count, min_frags) -> dict(pts, normals or None, count, nfrag), on host arrays, replaces the device
-    pass (tests).  clean: None, or a dict of yoho_amd.clean.statistical's keyword arguments (max_dist defaults to 4 voxels): the fused
+    pass (tests).  clean: None, or a dict of yoho_amd.clean.statistical's keyword arguments (max_dist defaults to 4 voxels) - or, with
+    "method": "cluster", of yoho_amd.cluster.keep_large's (eps defaults to 4 voxels; the key travels on to the cleaner) -: the fused
     rows that filter drops - strays that min_frags cannot reach where one fragment alone saw a region - are left out of the file, with
     their normals, count and nfrag; cleaner(out, clean) -> dict replaces clean_fused (tests).  -> (path, the dict written)"""
     from .run_dataset import result_dir
@@ -157,9 +163,11 @@ def write_scene_cloud(cfg, dataset, yoho_sign='YOHO_O_MW', voxel=0.025, min_frag
     fuse = _device_fuse(ctx) if fuse is None else fuse
     out = fuse(clouds, poses, voxel, min_count, min_frags)
     if clean is not None:
+        from . import clean as CL
         kw = dict(clean)
-        if kw.get("max_dist") is None:
-            kw["max_dist"] = 4.0 * float(voxel)
+        key = CL.method_of(kw)[1]
+        if kw.get(key) is None:
+            kw[key] = 4.0 * float(voxel)
         out = cleaner(out, kw) if cleaner is not None else clean_fused(ctx, out, kw)
     path = os.path.join(out_dir, 'scene.ply')
     write_ply(path, out["pts"], out.get("normals"), out["count"], out["nfrag"])

@@ -69,6 +69,8 @@ FUSE_MAX_POINTS = 1 << 26                   # YOHO_FUSE_MAX_POINTS
 # the entries of include/yoho_clean.h (k-NN inside a radius, the statistical outlier filter), kept apart for the same reason
 CLEAN_SYMBOLS = ["yoho_knn_within", "yoho_statistical_outliers"]
 KNN3_MAX = 32                               # YOHO_KNN3_MAX
+# the entry of include/yoho_cluster.h (exact DBSCAN labels), kept apart for the same reason
+CLUSTER_SYMBOLS = ["yoho_dbscan"]
 
 
 class ConvW(C.Structure):
@@ -114,7 +116,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS + CLUSTER_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -187,7 +189,8 @@ def load_library():
     lib.yoho_fuse_clouds.argtypes = [vp, vp, vp, ci, vp, vp, C.c_double, ci, ci, vp, vp, vp, vp, vp, C.c_int64, vp, vp]
     lib.yoho_knn_within.argtypes = [vp, vp, ci, vp, ci, C.c_float, ci, ci, vp, vp, vp, vp]
     lib.yoho_statistical_outliers.argtypes = [vp, vp, ci, C.c_float, ci, ci, C.c_double, vp, vp, vp, vp, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS:
+    lib.yoho_dbscan.argtypes = [vp, vp, ci, C.c_float, ci, vp, vp, vp, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS + CLUSTER_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -730,6 +733,26 @@ class Context:
                                                    C.c_void_p(count.data_ptr()) if want_count else None, C.c_void_p(keep.data_ptr()),
                                                    C.c_void_p(stats.data_ptr()), C.c_void_p(n_keep.data_ptr()), _stream()))
         return {"keep": keep, "mean_dist": mean_dist, "count": count, "stats": stats, "n_keep": n_keep}
+
+    # ---- density clusters (include/yoho_cluster.h) ----------------------------------------------
+    def dbscan(self, pts, eps, min_pts=4, want_count=True, want_core=True, want_sizes=True):
+        """pts (N,3) f32 -> dict(labels (N) int32, count (N) int32 or None, core (N) uint8 or None, sizes (N) int32 or None, n (3) int32 =
+        (clusters, core rows, noise rows)), device tensors: exact DBSCAN.  count = knn_within's other rows strictly inside eps, core =
+        finite and count + 1 >= min_pts, a cluster = a connected component of neighbouring core rows plus the border rows whose nearest
+        core neighbour (smallest (d2, index)) is in it, numbered by lowest core row; -1 = noise; sizes[c] = the members of cluster c, 0
+        behind the last (yoho_dbscan)."""
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError("dbscan: pts (N,3)")
+        N = pts.shape[0]
+        labels = torch.empty((N,), dtype=torch.int32, device=pts.device)
+        count = torch.empty((N,), dtype=torch.int32, device=pts.device) if want_count else None
+        core = torch.empty((N,), dtype=torch.uint8, device=pts.device) if want_core else None
+        sizes = torch.empty((N,), dtype=torch.int32, device=pts.device) if want_sizes else None
+        n = torch.empty((3,), dtype=torch.int32, device=pts.device)
+        _check(self._lib.yoho_dbscan(self._h, _dev(pts, torch.float32, "pts"), N, float(eps), int(min_pts), C.c_void_p(labels.data_ptr()),
+                                     C.c_void_p(count.data_ptr()) if want_count else None, C.c_void_p(core.data_ptr()) if want_core else None,
+                                     C.c_void_p(sizes.data_ptr()) if want_sizes else None, C.c_void_p(n.data_ptr()), _stream()))
+        return {"labels": labels, "count": count, "core": core, "sizes": sizes, "n": n}
 
     def refit_matches(self, k0, k1, T, inlier_dist, iters=4):
         """k0, k1 (M,3) f64 matched keypoints, T (3,4) f64 on the device (a winner of o_score / c_ransac chains in without a host read)

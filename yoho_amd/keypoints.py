@@ -37,14 +37,18 @@ def candidates(ctx, pc_d, voxel):
 
 def clean_candidates(ctx, sel, pts, voxel, clean):
     """the candidates that yoho_amd.clean.statistical keeps: clean is a dict of its keyword arguments, max_dist defaulting to 4 voxels
-    (it has to be given when voxel is None) -> (sel, pts) of the kept candidates, in their order"""
+    (it has to be given when voxel is None) -> (sel, pts) of the kept candidates, in their order.  An optional "method" key names
+    another filter of yoho_amd.clean.METHODS, "cluster" (yoho_amd.cluster.keep_large: eps defaults to 4 voxels) or "radius"; the
+    other keys are then that filter's arguments."""
     from . import clean as CL
     kw = dict(clean)
-    if kw.get("max_dist") is None:
+    method, key = CL.method_of(kw)
+    kw.pop("method", None)
+    if kw.get(key) is None:
         if voxel is None:
-            raise ValueError("select: clean needs max_dist when there is no voxel to take it from")
-        kw["max_dist"] = 4.0 * float(voxel)
-    kept = CL.statistical(ctx, pts, **kw)["sel"]
+            raise ValueError(f"select: clean needs {key} when there is no voxel to take it from")
+        kw[key] = 4.0 * float(voxel)
+    kept = CL.METHODS[method](ctx, pts, **kw)["sel"]
     return sel[kept], pts[kept].contiguous()
 
 
@@ -53,7 +57,8 @@ def select(ctx, pc_d, nkpts, voxel=None, start=0, clean=None):
     dist2 (k) f32), device tensors: farthest-point sampling (Context.fps) over candidates(ctx, pc_d, voxel), from candidate `start`.
     clean: None, or a dict of yoho_amd.clean.statistical's keyword arguments ({}: its defaults) - farthest-point sampling seeks out
     whatever lies far from everything, a stray first of all, so the candidates go through the outlier filter before the selection
-    (one more host read); `start` then counts the kept candidates."""
+    (one more host read); `start` then counts the kept candidates.  {"method": "cluster", "min_size": 100} filters by cluster size
+    instead (clean_candidates): strays that come in clumps pass the statistical filter."""
     sel, pts = candidates(ctx, pc_d, voxel)
     if clean is not None:
         sel, pts = clean_candidates(ctx, sel, pts, voxel, clean)
