@@ -1,7 +1,11 @@
 // The cell-sorted grid over a target cloud: its build (rf_key / rf_hist / rf_scan / rf_scatter / rf_cells_kernel, rf_grid_layout,
-// rf_build_grid).  What a query needs on the device (rf_cell, rf_slot, RfGrid, rf_walk) is inline in rfgrid.h; the users are
-// refine.hip (yoho_nn_within, yoho_icp_refine), plane.hip (yoho_estimate_normals, yoho_icp_plane) and verify.hip.  Compiled with
-// -ffp-contract=off like every file that includes rfgrid.h (yoho_amd/build.py).
+// rf_build_grid).  What a query needs on the device (rf_cell, rf_slot, RfGrid, rf_walk) is inline in rfgrid.h.  Six files build the
+// grid: refine.hip (yoho_nn_within, yoho_icp_refine), plane.hip (yoho_estimate_normals, yoho_icp_plane), verify.hip
+// (yoho_eval_transforms, yoho_verify_hypotheses), multiway.hip (yoho_edge_information), clean.hip (yoho_knn_within,
+// yoho_statistical_outliers) and cluster.hip (yoho_dbscan); refine, verify, multiway and plane.hip's ICP query it with rf_walk,
+// plane.hip's normals, clean.hip and cluster.hip walk start / pk with loops of their own.  fuse.hip and consist.hip include rfgrid.h for the shared
+// refusals only.  Compiled with -ffp-contract=off like every file that includes rfgrid.h (yoho_amd/build.py).  The digit passes at
+// both sides of their size thresholds: tests/test_gpu_sizes.py.
 //
 // THE GRID.  gridnn.hip's grid (linked lists behind an open-addressing table, a wave and 125 probes per query, brute force for what it
 // cannot settle) is built for queries that all have a partner nearby; in ICP half the cloud has none.  Here the targets are SORTED by
