@@ -47,12 +47,13 @@ def main(path):
             print("| kernel | grid (threads) | launches per pass | avg us, all 27 passes | avg us, every ninth pass (9th, 18th, 27th) |")
             print("|---|---|---|---|---|")
             tot_all = tot_9 = 0.0
-            for pat, per in (("fgemm3_kernel", None), ("fgemm3s_kernel", None), ("gft16x_kernel", None)):
+            for pat, per in (("fgemm3_kernel", None), ("fgemm3k_kernel", None), ("fgemm3s_kernel", None), ("gft16x_kernel", None)):
                 grids = [g for (g,) in db.execute(f"select distinct grid_x from kernels where name like '%{pat}%'")]
                 for g in sorted(grids):
                     rows = db.execute(f"select duration from kernels where name like '%{pat}%' and grid_x = ? order by {tcol}", (g,)).fetchall()
                     npass = 27
-                    # launches per pass: fgemm3 runs 32 -> 256 and 512 -> 256 on the smaller of its two grids, 256 -> 512 on the larger
+                    # launches per pass: fgemm3k runs 256 -> 512 and 512 -> 256 (one grid each), fgemm3 32 -> 256; in traces from before fgemm3k,
+                    # fgemm3 ran 32 -> 256 and 512 -> 256 on the smaller of its two grids, 256 -> 512 on the larger
                     k = 3 if pat == "gft16x_kernel" else (2 if (pat == "fgemm3_kernel" and len(grids) > 1 and g == min(grids)) else 1)
                     tail = [r[0] for r in rows[-npass * k:]]
                     if len(tail) < npass * k:

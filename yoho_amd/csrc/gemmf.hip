@@ -6,7 +6,8 @@
 //     Y[(i,o), (j,kp)] = sum_(m,c) A[(i,o), (m,c)] * B[(m,c), (j,kp)],      M = d*Cout, K = d*Cin, N = d*KPpad
 // (sum_r d^3 = 244 slab products instead of the 780 of the direct 13-tap form).  Both operands are kept as two fp16
 // planes (x * 2^s = hi + lo) and every term is evaluated as lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_f16 with
-// fp32 accumulation (error <= 3 * 2^-22 per product).
+// fp32 accumulation (error <= 3 * 2^-22 per product).  The two large layers (gemmf.h: fgemm_layer_k32) issue the same three products
+// on v_mfma_f32_16x16x32_f16, one MFMA per product and K32 stage (fgemmk_kernel below; gemmf2.hip: fgemm3k, fgemm2k).
 //
 // Blocking: 256 x 256 output tile per workgroup, 128 x 128 per wave (4 x 4 MFMA tiles, 256 accumulator registers),
 // K in stages of 32 = two MFMA sub-steps of 16.  Operands are stored in HBM already in the order the LDS wants them:
@@ -164,8 +165,57 @@ __global__ __launch_bounds__(256, 1) void fgemm_kernel(FGemmArgs a, int flags) {
     coef_epilogue(acc, row0, col0 % a.kppad, col0 / a.kppad, d, a.qbase[t], a.out, a.bias, a.descale, a.cout, a.nT32, a.rflag, lane, flags);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// fgemmk: this blocking for the layers of fgemm_layer_k32 - the products of fgemm3k in its order per accumulator (gemmf.h:
+// row_products32) on a plain loop over the same two 64 KiB stage buffers: per stage its products with the fragments read as they are
+// needed, `vmcnt(0)` + one barrier (stage s + 1 has landed, stage s is read), then the DMA of stage s + 2 into the freed buffer.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256, 1) void fgemmk_kernel(FGemmArgs a, int flags) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int t = 0, local = 0, r = 0;
+    if (!fg3_map(a, blockIdx.x & 7, blockIdx.x >> 3, t, local, r)) return;
+    const int d = a.dim[t];
+    const int MT = a.MT[t], KS = d * a.cin / 32;
+    const int cg = local / MT, mtile = local - cg * MT;
+    const int ntile = r + 8 * cg;
+    const char* Ag = a.A + a.a_off[t] + (size_t)mtile * KS * FG_STAGE;
+    const char* Bg = a.B + a.b_off[t] + (size_t)ntile * KS * FG_STAGE;
+    const int wm = w >> 1, wn = w & 1;
+    const int row0 = mtile * 256 + wm * 128, col0 = ntile * 256 + wn * 128;
+    const bool rows_live = row0 < d * a.cout;       // else: all 128 rows of this wave are padding
+    const int lane_a = (lane >> 4) * 4096 + (wm * 128 + (lane & 15)) * 16;
+    const int lane_b = FG_STAGE + (lane >> 4) * 4096 + (wn * 128 + (lane & 15)) * 16;
+
+    floatx4 acc[8][8];
+    zero_acc(acc);
+    stage_tile(Ag, smem, w, lane);
+    stage_tile(Bg, smem + FG_STAGE, w, lane);
+    if (KS > 1) {
+        stage_tile(Ag + FG_STAGE, smem + 2 * FG_STAGE, w, lane);
+        stage_tile(Bg + FG_STAGE, smem + 3 * FG_STAGE, w, lane);
+    }
+    if ((flags & EPI_RES) && rows_live) residual_start(acc, row0, col0 % a.kppad, col0 / a.kppad, d, a.qbase[t], a.res, a.descale, a.cout, a.nT32, lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int s = 0; s < KS; ++s) {
+        char* cur = smem + (s & 1) * (2 * FG_STAGE);
+        if (rows_live) stage32_plain<FG_STAGE / 2>(acc, cur + lane_a, cur + lane_b);
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
+        if (s + 2 < KS) {
+            stage_tile(uniform_ptr(Ag + (size_t)(s + 2) * FG_STAGE), cur, w, lane);
+            stage_tile(uniform_ptr(Bg + (size_t)(s + 2) * FG_STAGE), cur + FG_STAGE, w, lane);
+        }
+    }
+    if (rows_live) coef_epilogue(acc, row0, col0 % a.kppad, col0 / a.kppad, d, a.qbase[t], a.out, a.bias, a.descale, a.cout, a.nT32, a.rflag, lane, flags);
+}
+
 int fgemm_init() {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FG_LDS));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemmk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FG_LDS));
     if (int rc = cgemm_init()) return rc;
     return fgemm2_init();
 }
@@ -341,9 +391,13 @@ int launch_fgemm(const Layer& L, const char* Bplanes, int kppad, int nT32, const
     if (dbg_gemm1) blocking = FG_TILE256_W4;
     // fgemm3c and its fp8 weight pack - chosen AFTER every override of the blocking: the other kernels read A as fp16 planes
     if (blocking == FG_TILE256_W8 && amax && L.wpg8) { a.amax = amax; a.A = reinterpret_cast<const char*>(L.wpg8); }
+    // the two large layers run on the 16x16x32 MFMA in every blocking (fgemm3c keeps its own loop)
+    const char* dbg = experiment_env("YOHO_FGEMM_DEBUG");
+    if (fgemm_layer_k32(a) && !a.amax && !(dbg && std::strstr(dbg, "k16"))) flags |= F2_K32;
     if (blocking == FG_TILE256_W8) return launch_fgemm3(a, flags, s);
     if (blocking != FG_TILE256_W4) return launch_fgemm2(a, flags, s);
-    hipLaunchKernelGGL(fgemm_kernel, dim3(fgemm_grid(a, 1)), dim3(256), FG_LDS, s, a, flags);
+    if (flags & F2_K32) hipLaunchKernelGGL(fgemmk_kernel, dim3(fgemm_grid(a, 1)), dim3(256), FG_LDS, s, a, flags);
+    else hipLaunchKernelGGL(fgemm_kernel, dim3(fgemm_grid(a, 1)), dim3(256), FG_LDS, s, a, flags);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -300,6 +300,200 @@ __global__ __launch_bounds__(512, 2) void fgemm3_kernel(FGemmArgs a, int flags) 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// fgemm3k: fgemm3 for the two large layers (gemmf.h: fgemm_layer_k32) - its tile, work map and wave arrangement with the three products
+// on v_mfma_f32_16x16x32_f16 (gemmf.h: mfma_h16, row_products32 and the 16 x 16 accumulator mapping).  Same output tile per wave, same
+// MFMA cycles and same LDS read bytes as fgemm3's K16 loop; the chip holds a higher clock under this shape (profiles/fgemm_mfma_shape.md:
+// the A / B of the two loops; YOHO_FGEMM_DEBUG=k16 in the experiments build brings the K16 loop back for these layers).
+//
+// LDS: two buffers of one whole K32 stage (A 32 KiB | B 32 KiB, both in pack order [plane 2][k-group 4][row 256][16 B], so a stage is
+// eight straight 1 KiB pieces per wave), 128 KiB, one workgroup per CU as fgemm3.
+// Registers: 128 accumulators (floatx4 acc[8][4]), the stage's eight B fragments twice (current and next stage: 64), the two A fragments
+// of a 16-row block twice (this block and the next: 16).
+// K loop, stage s in buffer s & 1: block rows 0..6 (12 MFMAs each: lo.hi, hi.lo, hi.hi on the row's four accumulators, the next row's
+// two A fragments read behind the second and third); then `vmcnt(0)` + ONE barrier: every wave has all of stage s in registers and stage s + 1
+// (its DMA went out a whole stage ago) has landed; behind the barrier block row 7 with the ten fragment reads that open stage s + 1 and the
+// wave's eight DMA pieces of stage s + 2 into the buffer just freed.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int F3K_BUF = 2 * FG_STAGE;
+constexpr int F3K_LDS = 2 * F3K_BUF;
+
+struct Dma3k {
+    static constexpr int NP = 8;
+    int la, ldst;
+    __device__ __forceinline__ Dma3k(int w8, int lane) : la(w8 * 1024 + lane * 16), ldst(w8 * 1024) {}
+    template <int U>
+    __device__ __forceinline__ void piece(const char* srcA, const char* srcB, char* buf) const {
+        constexpr int q = (U & 3) * 8192;                                 // U = 0..3: A, 4..7: B; 8 KiB (eight waves) per piece index
+        if constexpr (U < 4) __builtin_amdgcn_global_load_lds((gptr_t)(srcA + q + la), (lptr_t)(buf + q + ldst), 16, 0, 0);
+        else __builtin_amdgcn_global_load_lds((gptr_t)(srcB + q + la), (lptr_t)(buf + FG_STAGE + q + ldst), 16, 0, 0);
+    }
+};
+struct FragsA32 { uintx4 al, ah; };            // one 16-row block of a stage
+struct FragsB32 { uintx4 bh[4], bl[4]; };      // the wave's four 16-column blocks of a stage
+
+// read R (0..9) of the fragments that open a stage: A lo of block row 0, B hi x4 (products lo.hi), A hi, B lo x4
+template <int R>
+__device__ __forceinline__ void read_open32(const char* pa, const char* pb, FragsA32& a0, FragsB32& b) {
+    if constexpr (R == 0) a0.al = *reinterpret_cast<const uintx4*>(pa + 16384);
+    else if constexpr (R < 5) b.bh[R - 1] = *reinterpret_cast<const uintx4*>(pb + (R - 1) * 256);
+    else if constexpr (R == 5) a0.ah = *reinterpret_cast<const uintx4*>(pa);
+    else b.bl[R - 6] = *reinterpret_cast<const uintx4*>(pb + 16384 + (R - 6) * 256);
+}
+
+// One K32 stage on B fragments `b` and A fragments read from pa (block row 0 already in fa[0]); npa / npb: the next stage in LDS, whose
+// opening fragments go to fa[0] / nb; DMA: the wave's pieces of the stage two ahead go to dmabuf (this stage's buffer)
+template <bool DMA>
+__device__ __forceinline__ void step32(const Dma3k& dm, floatx4 (&acc)[8][4], FragsA32 (&fa)[2], const FragsB32& b, FragsB32& nb, const char* pa,
+                                       const char* npa, const char* npb, const char* srcA, const char* srcB, char* dmabuf) {
+    sfor<0, 7>([&](auto ic) {
+        constexpr int i = decltype(ic)::value;
+        row_products32(acc[i], fa[i & 1].al, fa[i & 1].ah, b.bh, b.bl, [&](auto mc) {
+            constexpr int m = decltype(mc)::value;
+            // not behind MFMA 0: the compiler waits with lgkmcnt(0) only, and the row's first MFMA waits for its own fragments
+            if constexpr (m == 1) fa[(i + 1) & 1].al = *reinterpret_cast<const uintx4*>(pa + 16384 + (i + 1) * 256);
+            if constexpr (m == 2) fa[(i + 1) & 1].ah = *reinterpret_cast<const uintx4*>(pa + (i + 1) * 256);
+        });
+    });
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    row_products32(acc[7], fa[1].al, fa[1].ah, b.bh, b.bl, [&](auto mc) {
+        constexpr int m = decltype(mc)::value;
+        if constexpr (m < 5) {                  // two per MFMA: the next stage's first MFMA waits for all ten
+            read_open32<2 * m>(npa, npb, fa[0], nb);
+            read_open32<2 * m + 1>(npa, npb, fa[0], nb);
+        }
+        if constexpr (DMA && m >= 4) dm.template piece<m - 4>(srcA, srcB, dmabuf);
+    });
+}
+
+__global__ __launch_bounds__(512, 2) void fgemm3k_kernel(FGemmArgs a, int flags) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int t = 0, local = 0, r = 0;
+    if (!fg3_map(a, blockIdx.x & 7, blockIdx.x >> 3, t, local, r)) return;
+    const int d = a.dim[t];
+    const int MT = a.MT[t], KS = d * a.cin / 32;
+    const int cg = local / MT, mtile = local - cg * MT;
+    const int ntile = r + 8 * cg;
+    const char* Ag = a.A + a.a_off[t] + (size_t)mtile * KS * FG_STAGE;
+    const char* Bg = a.B + a.b_off[t] + (size_t)ntile * KS * FG_STAGE;
+    const int wm = (w8 & 3) >> 1, wn = w8 & 1, nh = w8 >> 2;            // Wave3's arrangement
+    const Dma3k dm(w8, lane);
+    const int lane_a = (lane >> 4) * 4096 + (wm * 128 + (lane & 15)) * 16;
+    const int lane_b = FG_STAGE + (lane >> 4) * 4096 + (nh * 128 + wn * 64 + (lane & 15)) * 16;
+
+    floatx4 acc[8][4];
+    zero_acc(acc);
+    auto dma = [&](int st, int buf) {
+        const char* sa = uniform_ptr(Ag + (size_t)st * FG_STAGE);
+        const char* sb = uniform_ptr(Bg + (size_t)st * FG_STAGE);
+        sfor<0, Dma3k::NP>([&](auto uc) { dm.template piece<decltype(uc)::value>(sa, sb, smem + buf); });
+    };
+    dma(0, 0);
+    if (KS > 1) dma(1, F3K_BUF);
+    const int row0 = mtile * 256 + wm * 128, colbase = ntile * 256 + nh * 128 + wn * 64;
+    const bool rows_live = row0 < d * a.cout;       // else: all 128 rows of this wave are padding
+    const int jidx = colbase / a.kppad, kp0 = colbase - jidx * a.kppad, qbase = a.qbase[t];
+    if ((flags & EPI_RES) && rows_live) residual_start(acc, row0, kp0, jidx, d, qbase, a.res, a.descale, a.cout, a.nT32, lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    if (!rows_live) {
+        // keep the wave's share of the DMA and the barriers going: one barrier per stage, as the live waves
+        for (int s = 0; s < KS; ++s) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (s + 2 < KS) dma(s + 2, (s & 1) * F3K_BUF);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        return;
+    }
+
+    FragsA32 fa[2];
+    FragsB32 P, Q;
+    sfor<0, 10>([&](auto rc) { read_open32<decltype(rc)::value>(smem + lane_a, smem + lane_b, fa[0], P); });
+    int s = 0, cur = 0;
+    auto run = [&](auto dmac, const FragsB32& b, FragsB32& nb) {
+        const int nxt = cur ^ F3K_BUF;
+        if constexpr (decltype(dmac)::value)
+            step32<true>(dm, acc, fa, b, nb, smem + cur + lane_a, smem + nxt + lane_a, smem + nxt + lane_b, uniform_ptr(Ag + (size_t)(s + 2) * FG_STAGE),
+                         uniform_ptr(Bg + (size_t)(s + 2) * FG_STAGE), smem + cur);
+        else    // the last two stages stage nothing; behind the last one the "next" fragments are read from the other buffer and never used
+            step32<false>(dm, acc, fa, b, nb, smem + cur + lane_a, smem + nxt + lane_a, smem + nxt + lane_b, nullptr, nullptr, nullptr);
+        cur = nxt; ++s;
+    };
+    constexpr std::true_type dmay;
+    constexpr std::false_type dman;
+    while (s + 2 < KS) {                       // KS is even (cin % 64 == 0, launch_fgemm3)
+        run(dmay, P, Q);
+        run(dmay, Q, P);
+    }
+    run(dman, P, Q);
+    run(dman, Q, P);
+    coef_epilogue(acc, row0, kp0, jidx, d, qbase, a.out, a.bias, a.descale, a.cout, a.nT32, a.rflag, lane, flags);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// fgemm2k: fgemm2's 256 x 128 tiles and work map for the layers of fgemm_layer_k32, so that the blockings stay bit-identical: the same
+// products in the same order per accumulator as fgemm3k (row_products32), on a plain loop - two buffers of one K32 stage (A 32 KiB |
+// the B half tile 16 KiB [plane 2][k-group 4][col 128][16 B]), 96 KiB: one workgroup per CU.  Per stage: the stage's products with the
+// fragments read as they are needed, `vmcnt(0)` + one barrier (stage s + 1 has landed, stage s is read), the DMA of stage s + 2.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int F2K_BUF = FG_STAGE + FG_STAGE / 2;
+constexpr int F2K_LDS = 2 * F2K_BUF;
+
+__global__ __launch_bounds__(256, 1) void fgemm2k_kernel(FGemmArgs a, int flags) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int t = 0, local = 0, r = 0;
+    if (!fg2_map(a, blockIdx.x & 7, blockIdx.x >> 3, (flags & F2_MIX) == 0, t, local, r)) return;
+    const int d = a.dim[t];
+    const int MT = a.MT[t], KS = d * a.cin / 32;
+    const int nh = local & 1, pair = local >> 1;
+    const int cg = pair / MT, mtile = pair - cg * MT;
+    const int ntile = r + 8 * cg;
+    const char* Ag = a.A + a.a_off[t] + (size_t)mtile * KS * FG_STAGE;
+    const char* Bg = a.B + a.b_off[t] + (size_t)ntile * KS * FG_STAGE + nh * 2048;
+    const int wm = w >> 1, wn = w & 1;
+    const int lane_a = (lane >> 4) * 4096 + (wm * 128 + (lane & 15)) * 16;
+    const int lane_b = FG_STAGE + (lane >> 4) * 2048 + (wn * 64 + (lane & 15)) * 16;
+
+    floatx4 acc[8][4];
+    zero_acc(acc);
+    // a wave's share of a stage: eight 1 KiB pieces of A, four of the B half (a (plane, k-group) unit of the half is a 2 KiB run of the pack)
+    auto dma = [&](int st, int buf) {
+        const char* sa = uniform_ptr(Ag + (size_t)st * FG_STAGE) + lane * 16;
+        const char* sb = uniform_ptr(Bg + (size_t)st * FG_STAGE) + lane * 16;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) __builtin_amdgcn_global_load_lds((gptr_t)(sa + (k * 4 + w) * 1024), (lptr_t)(smem + buf + (k * 4 + w) * 1024), 16, 0, 0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int pb = w * 4 + k, u = pb >> 1, part = pb & 1;
+            __builtin_amdgcn_global_load_lds((gptr_t)(sb + u * 4096 + part * 1024), (lptr_t)(smem + buf + FG_STAGE + u * 2048 + part * 1024), 16, 0, 0);
+        }
+    };
+    dma(0, 0);
+    if (KS > 1) dma(1, F2K_BUF);
+    const int row0 = mtile * 256 + wm * 128, colbase = ntile * 256 + nh * 128 + wn * 64;
+    const bool rows_live = row0 < d * a.cout;       // else: all 128 rows of this wave are padding
+    const int jidx = colbase / a.kppad, kp0 = colbase - jidx * a.kppad, qbase = a.qbase[t];
+    if ((flags & EPI_RES) && rows_live) residual_start(acc, row0, kp0, jidx, d, qbase, a.res, a.descale, a.cout, a.nT32, lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    for (int s = 0; s < KS; ++s) {
+        const int cur = (s & 1) * F2K_BUF;
+        if (rows_live) stage32_plain<FG_STAGE / 4>(acc, smem + cur + lane_a, smem + cur + lane_b);
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        if (s + 2 < KS) dma(s + 2, cur);
+    }
+    if (rows_live) coef_epilogue(acc, row0, kp0, jidx, d, qbase, a.out, a.bias, a.descale, a.cout, a.nT32, a.rflag, lane, flags);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // fgemm3c (gconv_mode 7, "fgemm8"; round 5, opt-in): fgemm3 with the two CORRECTION products of the fp16 split on the fp8 matrix pipe.
 // A product a * w is a_h w_h + a_h w_l + a_l w_h; the corrections are 2^-11 of the main term and survive e4m3 (3 mantissa bits: 2^-15
 // of the sum; tools/fp8_correction_study.py: 1.5e-5 worst relative error of the descriptor against 1.4e-6 and a tolerance of 1e-4).
@@ -714,6 +908,7 @@ int fgemm3_init() {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm3s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm3c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm3k_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F3K_LDS));
     return 0;
 }
 
@@ -728,6 +923,7 @@ int launch_fgemm3(const FGemmArgs& a, int flags, hipStream_t s) {
     static const bool small_ok = [] { const char* e = experiment_env("YOHO_FGEMM_DEBUG"); return !(e && std::strstr(e, "nosmall")); }();
     if (small_ok && a.cout == 32 && !(flags & EPI_RES)) hipLaunchKernelGGL(fgemm3s_kernel, dim3(tot), dim3(512), F3_LDS, s, a, flags);
     else if (a.amax) hipLaunchKernelGGL(fgemm3c_kernel, dim3(tot), dim3(512), F3_LDS, s, a, flags);      // gconv_mode 7: corrections on the fp8 pipe
+    else if (flags & F2_K32) hipLaunchKernelGGL(fgemm3k_kernel, dim3(tot), dim3(512), F3K_LDS, s, a, flags);
     else hipLaunchKernelGGL(fgemm3_kernel, dim3(tot), dim3(512), F3_LDS, s, a, flags);
     HIPCHK(hipGetLastError());
     return 0;
@@ -735,6 +931,7 @@ int launch_fgemm3(const FGemmArgs& a, int flags, hipStream_t s) {
 
 int fgemm2_init() {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F2_LDS));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm2k_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F2K_LDS));
     return fgemm3_init();
 }
 
@@ -747,7 +944,8 @@ int launch_fgemm2(const FGemmArgs& a, int flags, hipStream_t s) {
         if (std::strstr(dbg, "sparse4")) flags |= F2_SPARSE4;
         if (std::strstr(dbg, "sparse16")) flags |= F2_SPARSE16;
     }
-    hipLaunchKernelGGL(fgemm2_kernel, dim3(fgemm_grid(a, 2)), dim3(256), F2_LDS, s, a, flags);
+    if (flags & F2_K32) hipLaunchKernelGGL(fgemm2k_kernel, dim3(fgemm_grid(a, 2)), dim3(256), F2K_LDS, s, a, flags);
+    else hipLaunchKernelGGL(fgemm2_kernel, dim3(fgemm_grid(a, 2)), dim3(256), F2_LDS, s, a, flags);
     HIPCHK(hipGetLastError());
     return 0;
 }
