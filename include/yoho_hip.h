@@ -384,6 +384,12 @@ int yoho_set_partII_mode(yoho_ctx* ctx, int mode);
  * Fourier coefficients as fixed power-of-two multiples in fp16 planes (|activation| < 4094, |coefficient| < 16376).
  * Every kernel that writes such planes raises a device-side flag when a value falls outside; nothing else in the
  * forward calls changes (they stay asynchronous, and their outputs are then not to be trusted).
+ * Guarded, because they are written as planes: PartI modes 4-7 - the input's coefficients, the coefficients of every conv output
+ * (h0, mid, h2, y) and the activations in front of the three later convs with their coefficients; PartI mode 3 - the input and those
+ * activations; PartII modes 2-4 - the gathered input after BN + ReLU, the first layer's coefficients (h0) and the activations in front
+ * of the two cone layers.  NOT guarded, because they stay in fp32 from the accumulators to their consumer (BN + ReLU in the same
+ * epilogue, or the fp32 head) and no plane can overflow: the conv outputs of PartI mode 3, and PartII's cone-layer output (mid) and
+ * last conv output (h2).  tests/test_gpu_range_stages.py puts one channel of one stage outside at a time (profiles/precision.md).
  * yoho_range_status waits for `stream`, reports and clears the flag of every network whose out pointer is given (a NULL out
  * pointer leaves that network's flag pending for a later call) and returns YOHO_ERANGE if a reported flag was set, 0 otherwise; the caller then repeats the pass after yoho_set_gconv_mode(ctx, 1) /
  * yoho_set_partII_mode(ctx, 1) (bf16x3 planes carry the fp32 exponent range) - yoho_amd/hip.py does exactly that.

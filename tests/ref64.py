@@ -345,3 +345,205 @@ def partI_state_dict(name):
                 sd[k] = (sd[k] * np.float32(30.0)).astype(np.float32)
         return sd
     return W.synth_state_dict(W.PARTI_SPEC, {"seed7": 7, "seed11": 11, "seed23": 23}[name])
+
+
+# ----------------------------------------------------------------------------------------
+# one stage, one channel outside the fp16 planes: rescaled networks and the plan of a case (tests/test_gpu_range_stages.py)
+# ----------------------------------------------------------------------------------------
+# A power of two s moved between a layer and its consumer multiplies ONE channel of ONE stage by s and leaves every other value of the
+# network as it was, exactly (in float64 and in fp32 alike: a power of two commutes with every rounding away from the ends of the
+# exponent range).  kind 'conv': row o of the producing conv (weight and bias) times s, undone in the following BN (running_mean times
+# s, gamma over s; running_var stays, eps would break exactness) or, for PartII's h2, in column o of the FC head.  y has no consumer:
+# the output is normalised.  h2 carries the unscaled residual h0, so there the stage is not an exact multiple and the rescaled network
+# is a network of its own.  kind 'act': gamma and beta of the BN times s, input column o of the next conv over s.
+_P1, _R1, _R2 = "PartI_net.", "PartI_net.SO3_Conv_layers.0.", "PartII_SO3_Conv_layers.0."
+RESCALE = {
+    "partI": {
+        "a0": ("act", _R1 + "comb_layer_in.0", _R1 + "comb_layer_in.2"),
+        "mid": ("conv", _R1 + "comb_layer_in.2", _R1 + "comb_layer_out.0"),
+        "a1": ("act", _R1 + "comb_layer_out.0", _R1 + "comb_layer_out.2"),
+        "h2": ("conv", _R1 + "comb_layer_out.2", _P1 + "Conv_out.comb_layer.0"),
+        "a2": ("act", _P1 + "Conv_out.comb_layer.0", _P1 + "Conv_out.comb_layer.2"),
+        "y": ("conv", _P1 + "Conv_out.comb_layer.2", None),
+    },
+    "partII": {
+        "a_in": ("act", "Conv_init.comb_layer.0", "Conv_init.comb_layer.2"),
+        "a0": ("act", _R2 + "comb_layer_in.0", _R2 + "comb_layer_in.2"),
+        "mid": ("conv", _R2 + "comb_layer_in.2", _R2 + "comb_layer_out.0"),
+        "a1": ("act", _R2 + "comb_layer_out.0", _R2 + "comb_layer_out.2"),
+        "h2": ("conv", _R2 + "comb_layer_out.2", "PartII_To_R_FC.0"),
+    },
+}
+STAGE_COUT = {"partI": dict(a0=256, mid=512, a1=512, h2=256, a2=256, y=32), "partII": dict(a_in=128, a0=256, mid=512, a1=512, h2=256)}
+TWIN = 2.0                    # row factor of the mild twin of a case (the spiked row of a case is the row times MILD)
+
+
+def stage_kind(net, stage):
+    return RESCALE[net][stage][0]
+
+
+def rescale_stage(sd, net, stage, o, s):
+    """a COPY of the state dict in which channel `o` of `stage` is multiplied by the power of two `s` and nothing else changes"""
+    m, e = np.frexp(float(s))
+    assert m == 0.5 and s >= 1, "s must be a power of two"
+    kind, prod, cons = RESCALE[net][stage]
+    out = {k: np.array(v, copy=True) for k, v in sd.items()}
+    f = np.float32(s)
+    if kind == "conv":
+        out[prod + ".weight"][o] *= f
+        out[prod + ".bias"][o] *= f
+        if cons is None:
+            pass
+        elif cons + ".running_mean" in out:
+            out[cons + ".running_mean"][o] *= f
+            out[cons + ".weight"][o] /= f
+        else:
+            out[cons + ".weight"][:, o] /= f
+    else:
+        out[prod + ".weight"][o] *= f
+        out[prod + ".bias"][o] *= f
+        out[cons + ".weight"][:, o] /= f
+    return out
+
+
+def rescaled_stages(net, st, sd_r, stage, o, s, N):
+    """the float64 stage tensors of the rescaled network, from those of the base network `st` (same rows): channel o of `stage` times
+    s, everything else shared - except behind h2, whose tail (PartI: a2, y; PartII: t1, t2, q) is evaluated anew under `sd_r`"""
+    out = dict(st)
+    t = st[stage].copy()
+    if stage != "h2":
+        t[:, o] *= s
+        out[stage] = t
+        return out
+    t[:, o] = s * (st["h2"][:, o] - st["h0"][:, o]) + st["h0"][:, o]
+    out["h2"] = t
+    if net == "partI":
+        out["a2"] = _bn_relu(t, sd_r, _P1 + "Conv_out.comb_layer.0")
+        out["y"] = _conv(out["a2"], sd_r[_P1 + "Conv_out.comb_layer.2.weight"], sd_r[_P1 + "Conv_out.comb_layer.2.bias"], N)
+    else:
+        out["t1"] = _bn_relu_vec(_fc(t[:, :, 0], sd_r, "PartII_To_R_FC.0"), sd_r, "PartII_To_R_FC.1")
+        out["t2"] = _bn_relu_vec(_fc(out["t1"], sd_r, "PartII_To_R_FC.3"), sd_r, "PartII_To_R_FC.4")
+        out["q"] = _fc(out["t2"], sd_r, "PartII_To_R_FC.6")
+    return out
+
+
+def coef_floor(t):
+    """a LOWER bound on the largest |Fourier coefficient| of channels t (..., 60): the trivial coefficient is sqrt(60) * mean, and the
+    60 coefficients of a unitary transform cannot all lie under l2 / sqrt(60)"""
+    return float(np.max(np.maximum(np.sqrt(60.0) * np.abs(np.mean(t, axis=-1)), np.sqrt(np.sum(t * t, axis=-1) / 60.0))))
+
+
+def channel_outside(kind, t):
+    """how far OUTSIDE its plane the channel t (rows, 60) provably is (> 1: outside): activations by their largest value, conv outputs
+    by the lower bound on their largest coefficient"""
+    return float(np.max(np.abs(t))) / ACT_LIMIT if kind == "act" else coef_floor(t) / COEF_LIMIT
+
+
+def channel_inside(kind, t):
+    """how far INSIDE (> 1: inside): the l2 bound on the coefficients, and for activations the largest value as well (an activation
+    goes into a plane itself, and so do its coefficients)"""
+    c = COEF_LIMIT / max(float(np.max(np.sqrt(np.sum(t * t, axis=-1)))), 1e-300)
+    return min(c, ACT_LIMIT / max(float(np.max(np.abs(t))), 1e-300)) if kind == "act" else c
+
+
+def _scaled_channel(stage, st, o, s):
+    if stage == "h2":
+        return s * (st["h2"][:, o] - st["h0"][:, o]) + st["h0"][:, o]
+    return s * st[stage][:, o]
+
+
+def plan_stage_scale(net, stage, o, st_base, st_row, st_twin):
+    """the planner: from the float64 stages of the BASE network for the base batch, the spiked row and its mild twin -> the smallest
+    power of two s that puts channel o of `stage` a factor 2 outside its plane for the spiked row, or None where no such s leaves
+    the channel a factor 2 inside for every base row and for the twin (a dead ReLU channel, a channel whose bounds are too loose)"""
+    kind = stage_kind(net, stage)
+    for e in range(0, 24):
+        s = float(2 ** e)
+        if channel_outside(kind, _scaled_channel(stage, st_row, o, s)) >= 2.0:
+            ok = min(channel_inside(kind, _scaled_channel(stage, st_base, o, s)), channel_inside(kind, _scaled_channel(stage, st_twin, o, s))) >= 2.0
+            return s if ok else None
+    return None
+
+
+def stage_margins(net, stage, o, str_base, str_row, str_twin):
+    """the margins of a case from the float64 stages of the RESCALED network (rescaled_stages): 'out' - the spiked row's channel
+    outside; 'base' / 'twin' - the same channel of the base rows / the twin inside; 'rest' - every other stage and channel of every
+    row (base, spiked, twin) inside, by stage_extent.  A case is admissible iff all four are >= 2."""
+    kind = stage_kind(net, stage)
+
+    def rest(st):
+        t = st[stage].copy()
+        t[:, o] = 0.0
+        a, c = stage_extent(dict(st, **{stage: t}))
+        return min(ACT_LIMIT / a, COEF_LIMIT / c)
+    return dict(out=channel_outside(kind, str_row[stage][:, o]), base=channel_inside(kind, str_base[stage][:, o]),
+                twin=channel_inside(kind, str_twin[stage][:, o]), rest=min(rest(str_base), rest(str_row), rest(str_twin)))
+
+
+# the cases of tests/test_gpu_range_stages.py (tests/test_precision_cpu.py plans every one of them without a device).  Channels: every
+# slot of the 16 x 16 and of the 32 x 32 accumulator mapping - register o % 4, lane half o % 8 >= 4, second eight o % 16 >= 8, the next
+# 16-row block, either side of a wave's 128 rows and of a 256-row tile, the last channel.
+CHANNELS_ALL = (0, 3, 4, 7, 8, 15, 16, 127, 128, 255, -1)
+CHANNELS_FEW = (0, 7, 8, -1)
+# a prescribed channel the planner refuses (a dead ReLU channel, bounds too far apart), replaced by the next admissible one of its
+# residue class mod 16 (the same register, lane half and eight): {(network, stage, B, row, prescribed): chosen}
+CHANNEL_SUBST = {("partI", "h2", 33, 16, 4): 20}            # h2 channel 4: its bounds are too far apart for any power of two
+SWEEP_CHANNEL = 8                          # the channel of the keypoint sweeps
+SWEEP_ROWS = {33: (0, 15, 16, 31, 32), 257: (127, 128, 255, 256)}       # both 16-column tiles of a slab tile | wave halves, ragged tile
+
+
+def _chan(net, stage, B, row, o):
+    o = STAGE_COUT[net][stage] - 1 if o < 0 else o
+    return CHANNEL_SUBST.get((net, stage, B, row, o), o)
+
+
+def range_stage_cases():
+    """-> [(network, mode, stage, channel, B, row)], every case once"""
+    cases = []
+
+    def add(net, mode, stage, chans, B, row):
+        for o in chans:
+            c = (net, mode, stage, _chan(net, stage, B, row, o), B, row)
+            if c not in cases:
+                cases.append(c)
+    for stage in ("a0", "mid", "a1", "h2", "a2", "y"):
+        add("partI", "fgemm", stage, CHANNELS_ALL if stage in ("mid", "h2") else CHANNELS_FEW, 33, 16)
+    for stage in ("mid", "h2"):
+        for B, rows in SWEEP_ROWS.items():
+            for row in rows:
+                add("partI", "fgemm", stage, (SWEEP_CHANNEL,), B, row)
+    for mode in ("fgemm256", "fgemm128"):
+        for stage in ("a0", "mid", "a1", "h2", "a2", "y"):
+            add("partI", mode, stage, CHANNELS_FEW, 33, 16)
+    for stage in ("a0", "a1", "a2"):
+        add("partI", "fp16x2", stage, CHANNELS_FEW, 33, 16)
+    for stage in ("mid", "h2"):
+        add("partI", "fgemm8", stage, CHANNELS_FEW, 33, 16)
+    for mode in ("fp16x2", "cgemm"):
+        for stage in ("a_in", "a0", "mid", "a1", "h2"):
+            add("partII", mode, stage, CHANNELS_FEW, 33, 16)
+            add("partII", mode, stage, (SWEEP_CHANNEL,), 257, 128)
+    return cases
+
+
+def range_stage_plan(net, stage, o, B, row, sd, N, P=None):
+    """everything of a case that does not depend on the mode, from float64 alone (cached base passes; one-row passes for the spiked
+    row and the twin): dict(s, sd (rescaled), x / feats + pre (base inputs), margins, st (base, spiked, twin stages of the rescaled
+    network)), or None where the planner refuses the channel"""
+    if net == "partI":
+        x = partI_input(B)
+        st_b = partI_forward64(x, sd, N, stages=True)[2]
+        one = lambda f: partI_forward64(spike([x], row, f)[0][row:row + 1], sd, N, stages=True)[2]
+        inputs = dict(x=x)
+    else:
+        feats, pre = partII_input(B)
+        st_b = partII_forward64(*feats, pre, sd, N, P, stages=True)[1]
+        one = lambda f: partII_forward64(*[a[row:row + 1] for a in spike(feats, row, f)], pre[row:row + 1], sd, N, P, stages=True)[1]
+        inputs = dict(feats=feats, pre=pre)
+    st_r, st_t = one(MILD), one(TWIN)
+    s = plan_stage_scale(net, stage, o, st_b, st_r, st_t)
+    if s is None:
+        return None
+    sd_r = rescale_stage(sd, net, stage, o, s)
+    st = tuple(rescaled_stages(net, t, sd_r, stage, o, s, N) for t in (st_b, st_r, st_t))
+    return dict(inputs, s=s, sd=sd_r, margins=stage_margins(net, stage, o, *st), st=st)

@@ -161,3 +161,107 @@ def test_spiked_rows_leave_the_fp16_range_and_mild_ones_stay_inside(sd1, sd2, ta
                 assert R.stage_floor({k: st[k] for k in ("a_in", "h0", "a0", "mid", "a1", "h2")}, 0) > 2 * R.COEF_LIMIT, row
             else:
                 assert 2 * amax < R.ACT_LIMIT and 2 * cmax < R.COEF_LIMIT and amax > 10.0, (row, amax, cmax)
+
+
+# ---- one stage, one channel outside: the rescaled networks and the plan of tests/test_gpu_range_stages.py -----------------------------
+def _sd_of(net, sd1, sd2):
+    return sd1 if net == "partI" else sd2
+
+
+def test_range_stage_cases_are_all_admissible(sd1, sd2, tables):
+    """every (network, stage, channel, row, B) the GPU tests use has a power of two s with all four float64 margins >= 2 - nothing is
+    decided at run time there - and the table holds every mode, stage, channel slot and row the GPU file is to exercise"""
+    cases = R.range_stage_cases()
+    assert len(cases) == len(set(cases))
+    assert R.partI_state_dict("seed7").keys() == sd1.keys()
+    have = {(net, mode, stage) for net, mode, stage, *_ in cases}
+    want = {("partI", m, s) for m in ("fgemm", "fgemm256", "fgemm128") for s in ("a0", "mid", "a1", "h2", "a2", "y")}
+    want |= {("partI", "fp16x2", s) for s in ("a0", "a1", "a2")} | {("partI", "fgemm8", s) for s in ("mid", "h2")}
+    want |= {("partII", m, s) for m in ("fp16x2", "cgemm") for s in ("a_in", "a0", "mid", "a1", "h2")}
+    assert have == want
+    for stage, cout in (("mid", 512), ("h2", 256)):
+        got = {o for net, mode, st, o, B, row in cases if (net, mode, st, B, row) == ("partI", "fgemm", stage, 33, 16)}
+        for o in (0, 3, 4, 7, 8, 15, 16, 127, 128, 255, cout - 1):
+            assert any(g % 16 == o % 16 and (g == o or ("partI", stage, 33, 16, o) in R.CHANNEL_SUBST) for g in got), (stage, o)
+        rows = {(B, row) for net, mode, st, o, B, row in cases if (net, mode, st) == ("partI", "fgemm", stage)}
+        assert rows >= {(33, r) for r in (0, 15, 16, 31, 32)} | {(257, r) for r in (127, 128, 255, 256)}
+    for k, o in R.CHANNEL_SUBST.items():
+        assert o % 16 == k[4] % 16
+    seen = set()
+    for net, mode, stage, o, B, row in cases:
+        key = (net, stage, o, B, row)
+        if key in seen:
+            continue
+        seen.add(key)
+        assert 0 <= o < R.STAGE_COUT[net][stage] and 0 <= row < B
+        p = R.range_stage_plan(net, stage, o, B, row, _sd_of(net, sd1, sd2), tables.N, tables.P)
+        assert p is not None, key
+        m = p["margins"]
+        print("%-6s %-4s o=%3d B=%3d row=%3d  s=2^%-2d  out %.2f  base %.2f  twin %.2f  rest %.2f"
+              % (net, stage, o, B, row, int(np.log2(p["s"])), m["out"], m["base"], m["twin"], m["rest"]))
+        assert min(m.values()) >= 2.0, (key, m)
+
+
+EXACT = [("partI", s) for s in ("a0", "mid", "a1", "a2", "y")] + [("partII", s) for s in ("a_in", "a0", "mid", "a1")]
+
+
+def _two_rows(net, sd, tables):
+    """-> f(state dict) = (outputs, stages, fp32 oracle outputs) of rows 16 (times MILD) and 17 of the 33-row inputs"""
+    if net == "partI":
+        x = R.spike([R.partI_input(33)], 16, R.MILD)[0][16:18]
+        return lambda d: (R.partI_forward64(x, d, tables.N, stages=True)[:2], R.partI_forward64(x, d, tables.N, stages=True)[2],
+                          R.oracle_partI(x, d, tables.N))
+    feats, pre = R.partII_input(33)
+    fs = [a[16:18] for a in R.spike(feats, 16, R.MILD)]
+    return lambda d: ((R.partII_forward64(*fs, pre[16:18], d, tables.N, tables.P),), R.partII_forward64(*fs, pre[16:18], d, tables.N, tables.P, stages=True)[1],
+                      (R.oracle_partII(*fs, pre[16:18], d, tables.N, tables.P),))
+
+
+@pytest.mark.parametrize("net,stage", EXACT)
+def test_rescaled_network_is_the_base_network_but_for_one_channel(sd1, sd2, tables, net, stage):
+    """every float64 stage tensor of the rescaled network equals the base network's to 1e-12, stage S channel o is s times the base
+    bit for bit, and the fp32 oracle gives the same bits under both state dicts (a power of two commutes with its roundings too): the
+    GPU tests reuse the base batch's float64 pass and its e_ref.  y has no consumer: there the outputs differ and are not compared.
+    The helper returns copies and leaves its input alone."""
+    sd = _sd_of(net, sd1, sd2)
+    o, s = 7, 1024.0
+    keep = {k: v.copy() for k, v in sd.items()}
+    sd_r = R.rescale_stage(sd, net, stage, o, s)
+    assert all(np.array_equal(sd[k], keep[k]) for k in keep) and sd_r.keys() == sd.keys()
+    assert not any(np.shares_memory(sd_r[k], sd[k]) for k in sd)
+    changed = sorted(k for k in sd if not np.array_equal(sd_r[k], sd[k]))
+    assert len(changed) == (2 if stage == "y" else (4 if R.stage_kind(net, stage) == "conv" else 3)), changed
+    run = _two_rows(net, sd, tables)
+    (out0, st0, orc0), (out1, st1, orc1) = run(sd), run(sd_r)
+    for k in st0:
+        a, b = st0[k], st1[k]
+        if k == stage:
+            assert np.array_equal(b[:, o], s * a[:, o]) and np.abs(a[:, o]).max() > 0
+            a, b = np.delete(a, o, axis=1), np.delete(b, o, axis=1)
+        if stage == "y":
+            continue
+        assert np.abs(a - b).max() <= 1e-12 * np.abs(a).max(), (stage, k)
+    via = R.rescaled_stages(net, st0, sd_r, stage, o, s, tables.N)
+    assert all(np.array_equal(via[k], st1[k]) if k == stage else via[k] is st0[k] for k in st0)
+    if stage != "y":
+        for a, b in zip(out0, out1):
+            assert np.abs(a - b).max() <= 1e-12
+        for a, b in zip(orc0, orc1):
+            assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("net", ("partI", "partII"))
+def test_rescaled_h2_tail_is_the_full_pass(sd1, sd2, tables, net):
+    """h2 carries the unscaled residual: the rescaled network is one of its own.  rescaled_stages evaluates its tail from the base
+    stages (what the 257-row cases plan with); here against the full float64 pass under the rescaled state dict."""
+    sd = _sd_of(net, sd1, sd2)
+    o, s = 8, 512.0
+    sd_r = R.rescale_stage(sd, net, "h2", o, s)
+    run = _two_rows(net, sd, tables)
+    st0, st1 = run(sd)[1], run(sd_r)[1]
+    via = R.rescaled_stages(net, st0, sd_r, "h2", o, s, tables.N)
+    assert via.keys() == st1.keys()
+    for k in st1:
+        assert np.abs(via[k] - st1[k]).max() <= 1e-12 * np.abs(st1[k]).max(), k
+    res = st1["h2"][:, o] - s * (st0["h2"][:, o] - st0["h0"][:, o])
+    assert np.abs(res - st0["h0"][:, o]).max() <= 1e-9 * np.abs(st1["h2"][:, o]).max()        # s x the conv + the residual as it was
