@@ -9,7 +9,10 @@ once (in float64 the second normalisation of fcgf_feat.py:48 changes nothing).  
 `hook(name, x, W)` is called in front of every convolution (name = the state-dict prefix of its kernel: "conv1", "block1.conv1", ...,
 "conv4_tr", ..., "conv1_tr", "final"; x the float64 input rows, W the float64 kernel) and returns either `(x, W)` or a list of such
 pairs whose convolutions are summed - a split product is a sum of plane products, and one that leaves a cross term out cannot be
-written as one pair.  A pass with a hook is never cached.  `relu=` replaces the ReLU (np.maximum: NaN stays NaN).
+written as one pair.  A pass with a hook is never cached.  `relu=` replaces the ReLU (np.maximum: NaN stays NaN).  `bn_hook(name, x)` is
+called with the input rows of every BatchNorm (name = its state-dict prefix without ".bn": "norm1", "block1.norm1", ...) before its
+statistics are read from the state dict, so that a hook may write them there (tests/trained_like.py calibrates so); such a pass is not
+cached either.
 
 `emulate_fp16x2` is the hook that reproduces csrc/spconv.hip:split_pair_sp and csrc/sparse.hip:up_conv: activations through fp32, times
 16, hi = fp16(.), lo = fp16(. - hi); weights times 2^(10 - exponent of the largest), the same two planes; the product lo*Wh + hi*Wl +
@@ -112,7 +115,9 @@ def _memoised_oracle_maps():
 # ----------------------------------------------------------------------------------------
 # the float64 pass
 # ----------------------------------------------------------------------------------------
-def _bn(x, sd, name):
+def _bn(x, sd, name, bn_hook=None):
+    if bn_hook is not None:
+        bn_hook(name, x)
     g, b = sd[name + ".bn.weight"].astype(F64), sd[name + ".bn.bias"].astype(F64)
     m, v = sd[name + ".bn.running_mean"].astype(F64), sd[name + ".bn.running_var"].astype(F64)
     s = g / np.sqrt(v + EPS)
@@ -128,7 +133,7 @@ def swallowing_relu(x):
     return np.fmax(x, 0.0)
 
 
-def _forward64(coords, sd, k1, hook, relu):
+def _forward64(coords, sd, k1, hook, relu, bn_hook=None):
     (cs, maps) = _levels(coords)
     n = [len(c) for c in cs]
 
@@ -152,21 +157,24 @@ def _forward64(coords, sd, k1, hook, relu):
                 out = o if out is None else out + o
         return out
 
+    def bn(x, name):
+        return _bn(x, sd, name, bn_hook)
+
     def block(x, l, ts, name):
-        out = relu(_bn(conv(name + ".conv1", x, l, l, 3, ts), sd, name + ".norm1"))
-        out = _bn(conv(name + ".conv2", out, l, l, 3, ts), sd, name + ".norm2")
+        out = relu(bn(conv(name + ".conv1", x, l, l, 3, ts), name + ".norm1"))
+        out = bn(conv(name + ".conv2", out, l, l, 3, ts), name + ".norm2")
         return relu(out + x)
 
     x = np.ones((n[0], 1), F64)
-    s1 = block(_bn(conv("conv1", x, 0, 0, k1, 1), sd, "norm1"), 0, 1, "block1")
-    s2 = block(_bn(conv("conv2", relu(s1), 0, 1, 3, 1), sd, "norm2"), 1, 2, "block2")
-    s4 = block(_bn(conv("conv3", relu(s2), 1, 2, 3, 2), sd, "norm3"), 2, 4, "block3")
-    s8 = block(_bn(conv("conv4", relu(s4), 2, 3, 3, 4), sd, "norm4"), 3, 8, "block4")
-    out = block(_bn(conv("conv4_tr", relu(s8), 3, 2, 3, 4, True), sd, "norm4_tr"), 2, 4, "block4_tr")
+    s1 = block(bn(conv("conv1", x, 0, 0, k1, 1), "norm1"), 0, 1, "block1")
+    s2 = block(bn(conv("conv2", relu(s1), 0, 1, 3, 1), "norm2"), 1, 2, "block2")
+    s4 = block(bn(conv("conv3", relu(s2), 1, 2, 3, 2), "norm3"), 2, 4, "block3")
+    s8 = block(bn(conv("conv4", relu(s4), 2, 3, 3, 4), "norm4"), 3, 8, "block4")
+    out = block(bn(conv("conv4_tr", relu(s8), 3, 2, 3, 4, True), "norm4_tr"), 2, 4, "block4_tr")
     out = np.concatenate([relu(out), s4], 1)
-    out = block(_bn(conv("conv3_tr", out, 2, 1, 3, 2, True), sd, "norm3_tr"), 1, 2, "block3_tr")
+    out = block(bn(conv("conv3_tr", out, 2, 1, 3, 2, True), "norm3_tr"), 1, 2, "block3_tr")
     out = np.concatenate([relu(out), s2], 1)
-    out = block(_bn(conv("conv2_tr", out, 1, 0, 3, 1, True), sd, "norm2_tr"), 0, 1, "block2_tr")
+    out = block(bn(conv("conv2_tr", out, 1, 0, 3, 1, True), "norm2_tr"), 0, 1, "block2_tr")
     out = np.concatenate([relu(out), s1], 1)
     out = relu(conv("conv1_tr", out, 0, 0, 1, 1))
     out = conv("final", out, 0, 0, 1, 1) + sd["final.bias"].astype(F64)
@@ -186,10 +194,10 @@ def _cached(kind, coords, sd, k1, fn):
     return _CACHE[key]
 
 
-def resunet_forward64(coords, sd, conv1_kernel_size=7, hook=None, relu=None):
+def resunet_forward64(coords, sd, conv1_kernel_size=7, hook=None, relu=None, bn_hook=None):
     """coords (N,3) int distinct voxels -> (N, Cout) float64 unit rows, in input order"""
-    if hook is not None or relu is not None:
-        return _forward64(coords, sd, conv1_kernel_size, hook, relu or nan_relu)
+    if hook is not None or relu is not None or bn_hook is not None:
+        return _forward64(coords, sd, conv1_kernel_size, hook, relu or nan_relu, bn_hook)
     return _cached("f64", coords, sd, conv1_kernel_size, lambda: _forward64(coords, sd, conv1_kernel_size, None, nan_relu))
 
 

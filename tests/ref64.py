@@ -13,7 +13,10 @@ Results are cached per (state dict, input) at module scope, so that the modes of
 with it that the comparison below rejects subtly wrong results); a pass with a hook is never cached.  PartI calls it on
     a0 / a1 / a2   the activations relu(bn(.)) in front of the 256->512, the 512->256 and the 256->32 conv
     h0, mid, h2, y the outputs of the four convs (h2 after the residual)
-PartII on a_in, h0, a0, mid, a1, h2, t1, t2, q accordingly (t1 / t2: the activated 1x1 layers, q: the raw quaternion).
+PartII on a_in, h0, a0, mid, a1, h2, t1, t2, q accordingly (t1 / t2: the activated 1x1 layers, q: the raw quaternion), and on three
+tensors that are no stages (they are not among the returned stage tensors): x_in, the gathered input in front of the first BatchNorm,
+and f1 / f2, the outputs of the 1x1 layers in front of theirs.  With these every BatchNorm of both networks has its input passed to
+the hook before its statistics are read from the state dict: a hook may write them there (tests/trained_like.py calibrates so).
 """
 import hashlib
 import os
@@ -173,7 +176,7 @@ def partII_forward64(bf0, bf1, af0, af1, pre_idx, sd, N, P, stages=False, hook=N
         bi = np.arange(B)[:, None, None]
         fi = np.arange(bf0.shape[1])[None, :, None]
         xin = np.concatenate([bf0[bi, fi, perm[:, None, :]], bf1, af0[bi, fi, perm[:, None, :]], af1], axis=1)
-        x64 = np.asarray(xin, np.float32).astype(F64)
+        x64 = hk("x_in", np.asarray(xin, np.float32).astype(F64))
         r = "PartII_SO3_Conv_layers.0."
         a_in = hk("a_in", _bn_relu(x64, sd, "Conv_init.comb_layer.0"))
         h0 = hk("h0", _conv(a_in, sd["Conv_init.comb_layer.2.weight"], sd["Conv_init.comb_layer.2.bias"], N))
@@ -182,8 +185,8 @@ def partII_forward64(bf0, bf1, af0, af1, pre_idx, sd, N, P, stages=False, hook=N
         a1 = hk("a1", _bn_relu(mid, sd, r + "comb_layer_out.0"))
         h2 = hk("h2", _conv(a1, sd[r + "comb_layer_out.2.weight"], sd[r + "comb_layer_out.2.bias"], N) + h0)
         # the head keeps [:, :, 0, 0] of 1x1 layers: only group element 0 is ever read
-        t1 = hk("t1", _bn_relu_vec(_fc(h2[:, :, 0], sd, "PartII_To_R_FC.0"), sd, "PartII_To_R_FC.1"))
-        t2 = hk("t2", _bn_relu_vec(_fc(t1, sd, "PartII_To_R_FC.3"), sd, "PartII_To_R_FC.4"))
+        t1 = hk("t1", _bn_relu_vec(hk("f1", _fc(h2[:, :, 0], sd, "PartII_To_R_FC.0")), sd, "PartII_To_R_FC.1"))
+        t2 = hk("t2", _bn_relu_vec(hk("f2", _fc(t1, sd, "PartII_To_R_FC.3")), sd, "PartII_To_R_FC.4"))
         q = hk("q", _fc(t2, sd, "PartII_To_R_FC.6"))
         return q / np.sqrt(np.sum(q * q, axis=1))[:, None], dict(a_in=a_in, h0=h0, a0=a0, mid=mid, a1=a1, h2=h2, t1=t1, t2=t2, q=q)
     qn, st = _cached("partII", sd, [bf0, bf1, af0, af1, np.asarray(pre_idx), N, P], hook, run)
