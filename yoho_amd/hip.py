@@ -71,6 +71,10 @@ CLEAN_SYMBOLS = ["yoho_knn_within", "yoho_statistical_outliers"]
 KNN3_MAX = 32                               # YOHO_KNN3_MAX
 # the entry of include/yoho_cluster.h (exact DBSCAN labels), kept apart for the same reason
 CLUSTER_SYMBOLS = ["yoho_dbscan"]
+# the entry of include/yoho_disk.h (exact Poisson-disk thinning), kept apart for the same reason
+DISK_SYMBOLS = ["yoho_disk_sample"]
+DISK_MAX_ROUNDS = 64                        # YOHO_DISK_MAX_ROUNDS
+DISK_DEFAULT_ROUNDS = 16                    # Context.disk_sample's rounds per call (profiles/disk.md: what a scan needs, and the margin)
 
 
 class ConvW(C.Structure):
@@ -116,7 +120,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS + CLUSTER_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS + CLUSTER_SYMBOLS + DISK_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -190,7 +194,8 @@ def load_library():
     lib.yoho_knn_within.argtypes = [vp, vp, ci, vp, ci, C.c_float, ci, ci, vp, vp, vp, vp]
     lib.yoho_statistical_outliers.argtypes = [vp, vp, ci, C.c_float, ci, ci, C.c_double, vp, vp, vp, vp, vp, vp]
     lib.yoho_dbscan.argtypes = [vp, vp, ci, C.c_float, ci, vp, vp, vp, vp, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS + CLUSTER_SYMBOLS:
+    lib.yoho_disk_sample.argtypes = [vp, vp, ci, C.c_float, C.c_uint32, ci, ci, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS + CLUSTER_SYMBOLS + DISK_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -753,6 +758,26 @@ class Context:
                                      C.c_void_p(count.data_ptr()) if want_count else None, C.c_void_p(core.data_ptr()) if want_core else None,
                                      C.c_void_p(sizes.data_ptr()) if want_sizes else None, C.c_void_p(n.data_ptr()), _stream()))
         return {"labels": labels, "count": count, "core": core, "sizes": sizes, "n": n}
+
+    # ---- Poisson-disk thinning (include/yoho_disk.h) ---------------------------------------------
+    def disk_sample(self, pts, radius, seed=0, rounds=DISK_DEFAULT_ROUNDS, state=None):
+        """pts (N,3) f32 -> (state (N) uint8: 0 undecided, 1 kept, 2 dropped; n (3) int32 = (kept rows, rounds that ran, rows still
+        undecided)), device tensors: the maximal set of rows no two of which are closer than radius, greedy in the order of
+        key(i) = mix32(i ^ seed), by at most `rounds` synchronous rounds.  state=None starts afresh; a state that a call with the same
+        pts, radius and seed returned is continued IN PLACE (and returned) while n[2] > 0 (yoho_disk_sample)."""
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError("disk_sample: pts (N,3)")
+        N = pts.shape[0]
+        resume = state is not None
+        if resume:
+            if state.dtype != torch.uint8 or tuple(state.shape) != (N,) or not state.is_contiguous() or state.device != pts.device:
+                raise ValueError("disk_sample: state (N) uint8, contiguous, on the device of pts")
+        else:
+            state = torch.empty((N,), dtype=torch.uint8, device=pts.device)
+        n = torch.empty((3,), dtype=torch.int32, device=pts.device)
+        _check(self._lib.yoho_disk_sample(self._h, _dev(pts, torch.float32, "pts"), N, float(radius), int(seed) & 0xFFFFFFFF, int(rounds),
+                                          1 if resume else 0, C.c_void_p(state.data_ptr()), C.c_void_p(n.data_ptr()), _stream()))
+        return state, n
 
     def refit_matches(self, k0, k1, T, inlier_dist, iters=4):
         """k0, k1 (M,3) f64 matched keypoints, T (3,4) f64 on the device (a winner of o_score / c_ransac chains in without a host read)

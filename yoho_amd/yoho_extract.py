@@ -64,22 +64,33 @@ def _to_host(*tensors):
     return tuple(outs)
 
 
-KEYPOINT_MODES = ("random", "fps")
+KEYPOINT_MODES = ("random", "fps", "disk")
 
 
 class yoho_extractor():
     def __init__(self, fcgf_ckpt='model/Backbone/best_val_checkpoint.pth', yoho_ckpt='model/PartI_train/model_best.pth',
-                 fcgf=None, so3_dir=None, keypoints="random", keypoint_voxel=None, keypoint_clean=None):
+                 fcgf=None, so3_dir=None, keypoints="random", keypoint_voxel=None, keypoint_clean=None, keypoint_radius=None, keypoint_seed=0):
         """keypoints: "random" - the reference's np.random.permutation(len(pc))[0:nkpts] on numpy's global generator -, or "fps" -
         farthest-point sampling on the device (yoho_amd.keypoints.select) over the first point of every voxel of
         keypoint_voxel (None: the voxel_size of the call), from candidate 0: no draw from any generator, keypoints in pick order, a
         smaller nkpts a prefix of a larger one.  keypoint_clean ("fps" only): a dict of yoho_amd.clean.statistical's keyword arguments -
-        the candidates that filter drops are never picked (yoho_amd.keypoints.select's `clean`); None: no filter."""
+        the candidates that filter drops are never picked (yoho_amd.keypoints.select's `clean`); None: no filter.
+        "disk": exact Poisson-disk thinning of the same candidates at keypoint_radius (required, and refused in the other modes) with
+        priority seed keypoint_seed (yoho_amd.keypoints.select_disk): no two keypoints closer than the radius, every
+        candidate within the radius of one, in about a dozen parallel rounds instead of nkpts dependent picks; the number of
+        keypoints follows from the radius (keypoints.disk_radius calibrates it for a dataset) and nkpts only caps it;
+        keypoint_clean is accepted as in "fps"."""
         if keypoints not in KEYPOINT_MODES:
             raise ValueError(f"yoho_extractor: keypoints must be one of {KEYPOINT_MODES}, got {keypoints!r}")
-        if keypoint_clean is not None and keypoints != "fps":
-            raise ValueError(f"yoho_extractor: keypoint_clean filters the candidates of keypoints=\"fps\"; keypoints={keypoints!r} draws from the whole cloud")
+        if keypoint_clean is not None and keypoints not in ("fps", "disk"):
+            raise ValueError(f"yoho_extractor: keypoint_clean filters the candidates of keypoints=\"fps\" and \"disk\"; keypoints={keypoints!r} draws from the whole cloud")
+        if keypoints == "disk" and not (keypoint_radius is not None and float(keypoint_radius) > 0 and np.isfinite(float(keypoint_radius))):
+            raise ValueError(f"yoho_extractor: keypoints=\"disk\" needs a finite keypoint_radius > 0, got {keypoint_radius!r}")
+        if keypoints != "disk" and keypoint_radius is not None:
+            raise ValueError(f"yoho_extractor: keypoint_radius is the radius of keypoints=\"disk\"; keypoints={keypoints!r} takes none")
         self.keypoints = keypoints
+        self.keypoint_radius = None if keypoint_radius is None else float(keypoint_radius)
+        self.keypoint_seed = int(keypoint_seed)
         self.keypoint_clean = None if keypoint_clean is None else dict(keypoint_clean)
         self.keypoint_voxel = keypoint_voxel
         self.ctx = hip.get_context(so3_dir=so3_dir)
@@ -124,6 +135,13 @@ class yoho_extractor():
         dist, idx = self.ctx.nn_search(q, s, want_dist=False, squared=True)
         return f[idx]
 
+    def _select(self, ctx, pc_d, voxel_size, nkpts):
+        """the device selection of keypoints="fps" / "disk" on the current stream -> cloud indices (k) int64 on the device"""
+        voxel = voxel_size if self.keypoint_voxel is None else self.keypoint_voxel
+        if self.keypoints == "disk":
+            return KP.select_disk(ctx, pc_d, self.keypoint_radius, nkpts=nkpts, voxel=voxel, seed=self.keypoint_seed, clean=self.keypoint_clean)[0]
+        return KP.select(ctx, pc_d, nkpts, voxel=voxel, clean=self.keypoint_clean)[0]
+
     def _pass_starts(self, G):
         """first group element of every backbone pass, and G"""
         rb = self.rot_batch
@@ -145,16 +163,15 @@ class yoho_extractor():
         device depends on it until the first NN transfer - it is taken after one backbone pass per lane has been queued
         (YOHO_OVERLAP_DRAW=0: before the first pass).  It is the only draw in this method, so the generator is consumed exactly as
         in the reference (same keypoints for the same seed).
-        keypoints="fps": the selection is queued on lane 0 BEFORE the first pass (draw_ahead off): its one host read, the voxel count,
+        keypoints="fps" / "disk": the selection is queued on lane 0 BEFORE the first pass (draw_ahead off): its one host read, the voxel count,
         then waits for the upload alone and never for a backbone pass, and its k launches are in front of everything that needs
         them.  The indices stay on the device (kpts = None, kidx_d): _results reads them back with the descriptors."""
-        fps = self.keypoints == "fps"
+        fps = self.keypoints in ("fps", "disk")    # a selection on the device
         lanes = self.fcgf.lanes(self.lanes)
 
         def prepare(pc_d):                         # on lane 0's stream
             if fps:
-                kidx_d = KP.select(lanes[0][0], pc_d, nkpts, voxel=voxel_size if self.keypoint_voxel is None else self.keypoint_voxel,
-                                   clean=self.keypoint_clean)[0]
+                kidx_d = self._select(lanes[0][0], pc_d, voxel_size, nkpts)
                 kpts = None
             else:
                 kpts_index = np.random.permutation(len(pc))[0:nkpts]
@@ -256,10 +273,9 @@ class yoho_extractor():
         if hasattr(self.fcgf, "rotated_passes"):
             return self._extract_features_overlapped(pc, voxel_size, nkpts)
         # a backbone with run() only: the reference's host loop
-        if self.keypoints == "fps":
+        if self.keypoints in ("fps", "disk"):
             pc_d = torch.from_numpy(np.ascontiguousarray(np.asarray(pc, dtype=np.float64))).cuda()
-            kpts_index = KP.select(self.ctx, pc_d, nkpts, voxel=voxel_size if self.keypoint_voxel is None else self.keypoint_voxel,
-                                   clean=self.keypoint_clean)[0].cpu().numpy()
+            kpts_index = self._select(self.ctx, pc_d, voxel_size, nkpts).cpu().numpy()
         else:
             kpts_index = np.random.permutation(len(pc))[0:nkpts]
         kpts = pc[kpts_index]
