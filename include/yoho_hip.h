@@ -51,6 +51,7 @@
  *     YOHO_FCGF_COORDS=hash (yoho_set_fcgf_sort).   A/B and diagnostic switches without a setter (struct yoho_env_switches in
  *     csrc/common.h; every value gives valid results):   YOHO_PARTII_TAIL=staged, YOHO_TRANSFER=staged, YOHO_XF_STEAL=0,
  *     YOHO_NN_SPLITS=<n>, YOHO_FCGF=f32 (takes effect at the context's yoho_load_fcgf), YOHO_FCGF_MAPS=full, YOHO_FCGF_NORM=staged, YOHO_FCGF_HEADS=staged, YOHO_PARTII_L1=3 (PartII's first layer on the 256 x 256-tile GEMM kernel),
+ *     YOHO_PARTII_CONE=direct (PartII mode 2 keeps the direct 13-element cone kernel instead of the cone GEMM),
  *     YOHO_WS_LIMIT_MB=<n> (workspace requests above n MiB fail with YOHO_ENOMEM as on an exhausted device: test hook for the recoveries).
  *     The timing experiments YOHO_PARTI_DEBUG / YOHO_FGEMM_DEBUG exist only in the separate -DYOHO_EXPERIMENTS library, which no
  *     product code loads.
@@ -374,9 +375,10 @@ int yoho_set_nn_prefilter(yoho_ctx* ctx, int enable);
 int yoho_set_fcgf_sort(yoho_ctx* ctx, int parity_sort, int cell_sort);
 
 /* PartII group-conv layers: 0 = fp32 MFMA, 1 = bf16x3 split MFMA, 2 = fp16x2 split MFMA (first layer in the
- * group-Fourier domain, 13-rotation cone layer direct, last layer as one dense product at the identity), 3 = 2 with the
- * 13-rotation cone layer as ONE implicit GEMM over (tap, channel) whose B operand stages are picked per tap from the 45 cone
- * elements (YOHO_PARTII=cgemm), 4 = 3 with the two correction products of the fp16 split on the fp8 matrix pipe
+ * group-Fourier domain, 13-rotation cone layer as ONE implicit GEMM over (tap, channel) whose B operand stages are picked per tap
+ * from the 45 cone elements - or the direct cone kernel in a context created under YOHO_PARTII_CONE=direct, with the staged tail, or
+ * for a checkpoint the one-launch tail does not take -, last layer as one dense product at the identity), 3 = 2 with the cone GEMM
+ * whatever that switch says (YOHO_PARTII=cgemm; the same kernel and the same bits as 2 without the switch), 4 = 3 with the two correction products of the fp16 split on the fp8 matrix pipe
  * (YOHO_PARTII=cgemm8; quaternions ~1e-5 from the fp32 reference instead of ~1e-6, tolerance 1e-4; PartII feeds no index decision). */
 int yoho_set_partII_mode(yoho_ctx* ctx, int mode);
 

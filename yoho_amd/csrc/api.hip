@@ -357,7 +357,7 @@ int yoho_ctx_create(int device, const float* R, const uint8_t* N, const uint8_t*
         if ((rc = upload_slot_tables16(slab4.data(), unitg.data(), c->tabs)) || (rc = gconv16_init())) { delete c; return rc; }
     }
     c->gconv_mode = 4;      // default: group-Fourier irrep GEMMs on the fp16x2 split MFMA; YOHO_GCONV=f32 | bf16x3 | fourier | fp16x2 | fgemm
-    c->partII_mode = 2;     // default: fp16x2 cone layers; YOHO_PARTII=f32 | bf16x3 | fp16x2
+    c->partII_mode = 2;     // default: fp16x2 cone layers (the 13-element one as the cone GEMM); YOHO_PARTII=f32 | bf16x3 | fp16x2 | cgemm | cgemm8
     // ---- the environment is read HERE and nowhere else (include/yoho_hip.h lists the variables)
     {
         auto is = [](const char* name, const char* val) { const char* e = std::getenv(name); return e && std::strcmp(e, val) == 0; };
@@ -372,6 +372,7 @@ int yoho_ctx_create(int device, const float* R, const uint8_t* N, const uint8_t*
         c->env.fcgf_heads_staged = is("YOHO_FCGF_HEADS", "staged");
         if (const char* e = std::getenv("YOHO_WS_LIMIT_MB")) c->env.ws_limit_mb = std::atoll(e);
         if (is("YOHO_PARTII_L1", "3")) c->env.partII_l1_variant = FG_TILE256_W8;
+        c->env.partII_cone_direct = is("YOHO_PARTII_CONE", "direct");
     }
     if (const char* m = std::getenv("YOHO_FCGF_CELLS")) c->fcgf_cell_sort = std::atoi(m);
     if (const char* m = std::getenv("YOHO_FCGF_SORT")) c->fcgf_parity_sort = std::strcmp(m, "0") == 0 ? 0 : 1;
@@ -488,7 +489,7 @@ int yoho_load_partII(yoho_ctx* c, const yoho_partII_weights* w) {
     if ((rc = build_layer(c->p2[0], w->init, 128, 256, NTAP, &w->res_in_bn, c->fb))) return rc;      // + irrep-GEMM weights
     if ((rc = build_layer(c->p2[1], w->res_in, 256, 512, NTAP, &w->res_out_bn))) return rc;
     {
-        // the cone layer's weights once more as the A operand of the cone GEMM (PartII modes 3 / 4)
+        // the cone layer's weights once more as the A operand of the cone GEMM (PartII modes 2 / 3 / 4)
         std::vector<unsigned short> wc, wc8;
         if (pack_cgemm_weights(w->res_in.weight, 256, 512, NTAP, wc, &c->p2[1].wcg_descale, wc8)) { set_error("cone-GEMM weight packing failed"); return YOHO_EINVAL; }
         if ((rc = upload(wc.data(), wc.size() * sizeof(unsigned short), &c->p2[1].wcg))) return rc;
@@ -517,7 +518,7 @@ int yoho_set_partI_schedule(yoho_ctx* c, int chunk_kp, int streams) {
 }
 
 int yoho_set_partII_mode(yoho_ctx* c, int mode) {
-    if (!c || mode < 0 || mode > 4) { set_error("yoho_set_partII_mode: mode must be 0 (fp32 MFMA), 1 (bf16x3), 2 (fp16x2 MFMA, direct cone kernels), 3 (fp16x2, 13-element cone layer as an implicit GEMM) or 4 (3 with fp8 correction products)"); return YOHO_EINVAL; }
+    if (!c || mode < 0 || mode > 4) { set_error("yoho_set_partII_mode: mode must be 0 (fp32 MFMA), 1 (bf16x3), 2 (fp16x2 MFMA, 13-element cone layer as an implicit GEMM unless YOHO_PARTII_CONE=direct), 3 (2 with the cone GEMM whatever that switch says) or 4 (3 with fp8 correction products)"); return YOHO_EINVAL; }
     c->partII_mode = mode;
     return 0;
 }
@@ -947,8 +948,10 @@ static int partII_pass16(yoho_ctx* c, const float* s0, const float* s1, const fl
     const int nT16 = (M + 15) / 16, nT = (M + TILE - 1) / TILE;
     const size_t ch16 = (size_t)npl * 15360;
     const size_t n128 = (size_t)nT * 16, n256 = (size_t)nT * 32, n512 = (size_t)nT * 64, n32 = (size_t)nT * 4;
-    // (PartII modes 3 / 4 keep the cone GEMM's stage blocks where the direct kernels keep their 256-channel planes: whole 256-match column tiles)
-    const size_t szG = c->partII_mode >= 3 ? (size_t)((nT + 7) / 8) * c->cone_nslot * 8 * 32768 : 0;
+    // (PartII modes 2 / 3 / 4 keep the cone GEMM's stage blocks where the direct kernels keep their 256-channel planes: whole 256-match column tiles)
+    // mode 2 (the default) runs the same cone GEMM unless YOHO_PARTII_CONE=direct keeps gconv16_kernel<7,4,2> for it
+    const bool cone_gemm = c->partII_mode >= 3 || (c->partII_mode == 2 && !c->env.partII_cone_direct);
+    const size_t szG = cone_gemm ? (size_t)((nT + 7) / 8) * c->cone_nslot * 8 * 32768 : 0;
     const size_t szX = (size_t)nT16 * 16 * ch16, szA0 = std::max((size_t)nT16 * 32 * ch16, szG);
     const size_t szA1p = npl == 2 ? (size_t)nT16 * 64 * ch16 : 0;      // fp16x2: 13-cone activation planes for cone1_kernel
     int rc;
@@ -978,8 +981,8 @@ static int partII_pass16(yoho_ctx* c, const float* s0, const float* s1, const fl
         // less than half of the 45-element cone the direct kernel computes
         if ((rc = launch_head2(s0, s1, s2, s3, idx, c->dP, c->p2_init_bn_s, c->p2_init_bn_t, M, nT, bP, kppad, c->dF16, s, ridx, istride, rf))) return rc;
         if ((rc = launch_fgemm(c->p2[0], bP, kppad, nT, nullptr, bC, 0, s, rf, c->env.partII_l1_variant))) return rc;
-        if (c->partII_mode >= 3 && c->p2[1].wcg && !c->env.partII_tail_staged && mlp_head_supported(c->p2[3], c->p2[4], c->p2[5])) {
-            // modes 3 / 4: the 13-element cone layer as ONE implicit GEMM (cgemm_kernel, gemmf2.hip).  The inverse transform leaves the 45
+        if (cone_gemm && c->p2[1].wcg && !c->env.partII_tail_staged && mlp_head_supported(c->p2[3], c->p2[4], c->p2[5])) {
+            // modes 2 / 3 / 4: the 13-element cone layer as ONE implicit GEMM (cgemmk_kernel / cgemm_kernel<true>, gemmf2.hip).  The inverse transform leaves the 45
             // cone elements of the first layer's output as B-operand stage blocks [column tile][slot][32-channel block][32 KiB] (in the
             // region the direct kernels' planes bA0 occupy: 45 of 60 slabs, the same bytes per match), the GEMM writes cone1's planes
             const int nslot = c->cone_nslot;

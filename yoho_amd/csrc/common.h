@@ -300,6 +300,7 @@ struct yoho_env_switches {
     bool fcgf_norm_staged = false;     // YOHO_FCGF_NORM=staged: row normalisation as its own kernel behind the last convolution
     bool fcgf_heads_staged = false;    // YOHO_FCGF_HEADS=staged: the decoder's two 1 x 1 heads as two launches (heads_fused_kernel off); identical bits
     yoho::FGemmBlocking partII_l1_variant = yoho::FG_TILE128;   // YOHO_PARTII_L1=3: PartII's first (Fourier) layer on fgemm3 (FG_TILE256_W8) instead of fgemm2
+    bool partII_cone_direct = false;   // YOHO_PARTII_CONE=direct: PartII mode 2 keeps the direct 13-element cone kernel (gconv16_kernel<7,4,2>) instead of the cone GEMM
     long long ws_limit_mb = 0;         // YOHO_WS_LIMIT_MB=<n>: a workspace request above n MiB fails as an exhausted device would (0 = no limit):
                                        // lets a test walk the YOHO_ENOMEM recoveries of the backbone (hash-table attempt, table voxelisation)
 };
@@ -321,8 +322,9 @@ struct yoho_ctx {
     yoho::Layer p1[4];           // conv_in, res_in, res_out, conv_out
     yoho::Layer p2[6];           // init, res_in, res_out, fc0, fc1, fc2
     float *p2_init_bn_s = nullptr, *p2_init_bn_t = nullptr;  // BN(128) applied by the PartII pack kernel
-    int partII_mode = 2;         // cone layers: 0 fp32 MFMA, 1 bf16x3 split MFMA, 2 fp16x2 split MFMA (direct cone kernels), 3 fp16x2 with the 13-element cone
-                                 // layer as an implicit GEMM (cgemm_kernel), 4 = 3 with fp8 correction products
+    int partII_mode = 2;         // cone layers: 0 fp32 MFMA, 1 bf16x3 split MFMA, 2 fp16x2 split MFMA (default: the 13-element cone layer as an implicit GEMM,
+                                 // cgemmk_kernel; the direct cone kernel where the one-launch tail is off or with YOHO_PARTII_CONE=direct), 3 = 2 with the cone
+                                 // GEMM whatever the switch says, 4 = 3 with fp8 correction products (cgemm_kernel<true>)
     int cone_nslot = 0;          // group elements the middle cone layer reads (45 for the icosahedral tables), their slot (or -1) per element,
     int cone_slot_of[60];        // the slot of N[n_j][k] per (output element j, tap k), and the output elements n_j = N[0][j]
     unsigned char cone_slot[13 * 13];

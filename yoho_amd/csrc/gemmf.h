@@ -1,7 +1,7 @@
 // Shared by the irrep-GEMM kernels (gemmf.hip: fgemm_kernel, 256 x 256 tiles, one four-wave workgroup per CU; gemmf2.hip: fgemm2_kernel,
-// 256 x 128 tiles, two workgroups per CU, fgemm3 / fgemm3c / fgemm3s, 256 x 256 tiles in eight waves, and the cone GEMM cgemm_kernel):
+// 256 x 128 tiles, two workgroups per CU, fgemm3 / fgemm3c / fgemm3s, 256 x 256 tiles in eight waves, and the cone GEMMs cgemm_kernel / cgemmk_kernel):
 // operand pack constants, launch arguments, the tile work map, the residual start and the coefficient epilogue - for the 32 x 32 x 16
-// MFMA of the K16 loops and for the 16 x 16 x 32 MFMA of the large layers' K32 loops (fgemmk, fgemm2k, fgemm3k), whose product order is here.
+// MFMA of the K16 loops and for the 16 x 16 x 32 MFMA of the large layers' K32 loops (fgemmk, fgemm2k, fgemm3k, cgemmk), whose product order is here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>

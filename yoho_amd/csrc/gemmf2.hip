@@ -681,7 +681,7 @@ __global__ __launch_bounds__(512, 2) void fgemm3c_kernel(FGemmArgs a, int flags)
 // fp8 correction operand in place of the lo plane for FP8, hi + lo planes else).  Tile shape, LDS image, DMA, fragment reads and the
 // products are fgemm3c's / fgemm3's (three fp16 products, or one fp16 product + the two corrections on the fp8 pipe); the epilogue
 // applies bias, the next layer's BN + ReLU and writes fp16x2 planes in the layout cone1_kernel stages from
-// ([tile16][c8][plane][60 slabs][16 matches][8 ch], slab n_j).  Replaces gconv16_kernel<7,4,2> in PartII modes 3 / 4: no tap-pair or
+// ([tile16][c8][plane][60 slabs][16 matches][8 ch], slab n_j).  Replaces gconv16_kernel<7,4,2> in PartII modes 2 / 3 / 4 (fp16x2 products: on cgemmk_kernel's K32 stage loop, below): no tap-pair or
 // unit padding (14 / 13 twice), both operands blocked through LDS.
 // ---------------------------------------------------------------------------------------------------------------
 struct CGemmArgs {
@@ -782,9 +782,117 @@ __global__ __launch_bounds__(512, 2) void cgemm_kernel(CGemmArgs a) {
     note_range_bits(a.rflag, top, FP16_MAX);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// cgemmk: the fp16x2 cone GEMM (cgemm_kernel<false>'s work map, operand packs and sums) on fgemm3k's K32 stage loop: step32 with
+// row_products32 on v_mfma_f32_16x16x32_f16, two whole-stage buffers (128 KiB), one barrier per stage, the DMA one stage ahead.  The
+// packs are K32-stage blocks of 32 KiB already, so a stage is still eight straight 1 KiB pieces per wave; the B stage base is chosen per
+// K32 stage: a tap is KSt = cin / 32 whole stages, so the tap's slot is constant within a stage (stage s: tap s / KSt, channel block
+// s % KSt).  K = 13 taps x cin is the longest K loop of the project (104 stages for cin = 256).  The stages come in pairs (the two B
+// fragment sets trade places): ntap * KSt must be even, launch_cgemm keeps the K16 kernel otherwise.
+// Epilogue on the 16 x 16 accumulator mapping (gemmf.h): lane (col = lane & 15, g = lane >> 4), reg e -> row = 4 g + e: the four registers
+// of a lane are four consecutive output channels (second four of their eight when g is odd) of ONE match, 8 bytes per plane, and a
+// 16-column tile is one 16-match tile of cone1's planes; bias, BN + ReLU, H2_ASCALE, the hi / lo split and the range word as cgemm_kernel.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512, 2) void cgemmk_kernel(CGemmArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int tapoff[16];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int xcd = blockIdx.x & 7, slot_ = blockIdx.x >> 3;                // cgemm_kernel's work map
+    const int ct = xcd + 8 * (slot_ / a.MT), mtile = slot_ % a.MT;
+    if (ct >= a.nj * a.NTm) return;
+    const int j = ct / a.NTm, mt = ct - j * a.NTm;
+    const int KS = a.ntap * a.KSt;                                       // K32 stages (even, launch_cgemm)
+    if (tid < 16) tapoff[tid] = tid < a.ntap ? (int)a.slot[j * 13 + tid] : 0;
+    const char* Ag = a.A + (size_t)mtile * KS * FG_STAGE;
+    const char* Bt = a.B + (size_t)mt * a.nslot * a.KSt * FG_STAGE;      // this column tile's slots
+    __syncthreads();
+    auto bsrc = [&](int st) -> const char* {
+        const int tap = st / a.KSt, cb = st - tap * a.KSt;
+        const int sl = __builtin_amdgcn_readfirstlane(tapoff[tap]);
+        return uniform_ptr(Bt + ((size_t)sl * a.KSt + cb) * FG_STAGE);
+    };
+    const int wm = (w8 & 3) >> 1, wn = w8 & 1, nh = w8 >> 2;            // Wave3's arrangement
+    const Dma3k dm(w8, lane);
+    const int lane_a = (lane >> 4) * 4096 + (wm * 128 + (lane & 15)) * 16;
+    const int lane_b = FG_STAGE + (lane >> 4) * 4096 + (nh * 128 + wn * 64 + (lane & 15)) * 16;
+
+    floatx4 acc[8][4];
+    zero_acc(acc);
+    auto dma = [&](int st, int buf) {
+        const char* sa = uniform_ptr(Ag + (size_t)st * FG_STAGE);
+        const char* sb = bsrc(st);
+        sfor<0, Dma3k::NP>([&](auto uc) { dm.template piece<decltype(uc)::value>(sa, sb, smem + buf); });
+    };
+    dma(0, 0);
+    dma(1, F3K_BUF);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    FragsA32 fa[2];
+    FragsB32 P, Q;
+    sfor<0, 10>([&](auto rc) { read_open32<decltype(rc)::value>(smem + lane_a, smem + lane_b, fa[0], P); });
+    int s = 0, cur = 0;
+    auto run = [&](auto dmac, const FragsB32& b, FragsB32& nb) {
+        const int nxt = cur ^ F3K_BUF;
+        if constexpr (decltype(dmac)::value)
+            step32<true>(dm, acc, fa, b, nb, smem + cur + lane_a, smem + nxt + lane_a, smem + nxt + lane_b, uniform_ptr(Ag + (size_t)(s + 2) * FG_STAGE),
+                         bsrc(s + 2), smem + cur);
+        else    // the last two stages stage nothing; behind the last one the "next" fragments are read from the other buffer and never used
+            step32<false>(dm, acc, fa, b, nb, smem + cur + lane_a, smem + nxt + lane_a, smem + nxt + lane_b, nullptr, nullptr, nullptr);
+        cur = nxt; ++s;
+    };
+    constexpr std::true_type dmay;
+    constexpr std::false_type dman;
+    while (s + 2 < KS) {
+        run(dmay, P, Q);
+        run(dmay, Q, P);
+    }
+    run(dman, P, Q);
+    run(dman, Q, P);
+
+    // ---- epilogue: v = acc * descale + bias; the next layer's BN + ReLU; x H2_ASCALE; hi / lo planes; 8 bytes (4 channels) per plane and lane
+    // (the lane is made opaque here: the store addresses derived from it must not be hoisted above the K loop, whose registers are full)
+    int etid = threadIdx.x;
+    asm volatile("" : "+v"(etid));
+    const int g4 = (etid >> 4) & 3, c16 = etid & 15;
+    const int g = a.outg[j];
+    const int col0 = mt * 256 + nh * 128 + wn * 64;
+    unsigned top = 0u;
+#pragma unroll
+    for (int ai = 0; ai < 8; ++ai) {
+        const int o = mtile * 256 + wm * 128 + ai * 16 + g4 * 4;
+        const floatx4 b4 = *reinterpret_cast<const floatx4*>(a.bias + o);
+        const floatx4 s4 = *reinterpret_cast<const floatx4*>(a.bn_s + o);
+        const floatx4 t4 = *reinterpret_cast<const floatx4*>(a.bn_t + o);
+#pragma unroll
+        for (int bi = 0; bi < 4; ++bi) {
+            const int m0 = col0 + bi * 16;                                // first match of the 16-column tile (wave uniform)
+            // columns past the last 32-match tile were never written by the inverse transform (stale or foreign bytes): skipped before
+            // they reach the range word, as in cgemm_kernel
+            if ((m0 >> 5) >= a.nT32 || (m0 >> 4) >= a.nTiles16) continue;
+            float y[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float v = acc[ai][bi][e] * a.descale + b4[e];
+                y[e] = fmaxf(v * s4[e] + t4[e], 0.f) * H2_ASCALE;
+                top = max(top, __float_as_uint(y[e]) & 0x7FFFFFFFu);
+            }
+            unsigned h0, l0, h1, l1;
+            cg_split_pair(y[0], y[1], h0, l0);
+            cg_split_pair(y[2], y[3], h1, l1);
+            char* dst = a.out + (((size_t)(m0 >> 4) * a.c8out + (o >> 3)) * 2) * 15360 + g * 256 + c16 * 16 + (g4 & 1) * 8;
+            *reinterpret_cast<uint2*>(dst) = uint2{h0, h1};
+            *reinterpret_cast<uint2*>(dst + 15360) = uint2{l0, l1};
+        }
+    }
+    note_range_bits(a.rflag, top, FP16_MAX);
+}
+
 int cgemm_init() {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cgemm_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cgemm_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cgemmk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F3K_LDS));
     return 0;
 }
 
@@ -804,7 +912,12 @@ int launch_cgemm(const Layer& L, const char* Bstages, int nslot, const unsigned 
     std::memcpy(a.outg, outg, 13);
     const int CT = a.nj * a.NTm;
     const int grid = 8 * ((CT + 7) / 8) * a.MT;
+    // the fp16x2 products run on the K32 stage loop (cgemmk_kernel; profiles/cone_gemm_k32.md); YOHO_FGEMM_DEBUG=k16 in the experiments
+    // build brings the K16 loop back, as for fgemm3k.  The fp8 corrections keep their loop.
+    const char* dbg = experiment_env("YOHO_FGEMM_DEBUG");
+    const bool k32 = !fp8 && (a.ntap * a.KSt) % 2 == 0 && !(dbg && std::strstr(dbg, "k16"));
     if (fp8) hipLaunchKernelGGL(cgemm_kernel<true>, dim3(grid), dim3(512), F3_LDS, s, a);
+    else if (k32) hipLaunchKernelGGL(cgemmk_kernel, dim3(grid), dim3(512), F3K_LDS, s, a);
     else hipLaunchKernelGGL(cgemm_kernel<false>, dim3(grid), dim3(512), F3_LDS, s, a);
     HIPCHK(hipGetLastError());
     return 0;

@@ -1198,7 +1198,7 @@ class Context:
         _check(self._lib.yoho_set_partI_schedule(self._h, int(chunk_kp), int(streams)))
 
     def set_partII_mode(self, mode):
-        """'f32', 'bf16x3', 'fp16x2' (direct cone kernels), 'cgemm' (13-element cone layer as an implicit GEMM) or 'cgemm8' (cgemm with fp8
+        """'f32', 'bf16x3', 'fp16x2' (13-element cone layer as an implicit GEMM; the direct cone kernel with YOHO_PARTII_CONE=direct), 'cgemm' (the same GEMM whatever that switch says) or 'cgemm8' (cgemm with fp8
         correction products) for PartII (include/yoho_hip.h: yoho_set_partII_mode)."""
         _check(self._lib.yoho_set_partII_mode(self._h, PARTII_MODES[mode]))
         self.partII_mode = mode
