@@ -19,11 +19,11 @@ LIBDIR = os.path.join(PKG, "lib")
 EXPERIMENTS = os.environ.get("YOHO_EXPERIMENTS") == "1"
 OBJDIR = os.path.join(LIBDIR, "exp") if EXPERIMENTS else LIBDIR
 LIB = os.path.join(LIBDIR, "libyoho_hip_exp.so" if EXPERIMENTS else "libyoho_hip.so")
-SOURCES = ["api.hip", "gconv.hip", "gconv16.hip", "fourier.hip", "gemmf.hip", "gemmf2.hip", "gft16.hip", "cone1.hip", "sparse.hip", "spmaps.hip", "spconv.hip", "train.hip", "layout.hip", "match.hip", "matchf.hip", "gridnn.hip", "estim.hip", "pair.hip", "knn.hip", "radius.hip", "rfgrid.hip", "refine.hip", "plane.hip", "verify.hip", "consist.hip", "keypoints.hip", "multiway.hip", "fuse.hip", "clean.hip", "cluster.hip", "disk.hip"]
+SOURCES = ["api.hip", "gconv.hip", "gconv16.hip", "fourier.hip", "gemmf.hip", "gemmf2.hip", "gft16.hip", "cone1.hip", "sparse.hip", "spmaps.hip", "spconv.hip", "train.hip", "layout.hip", "match.hip", "matchf.hip", "gridnn.hip", "estim.hip", "pair.hip", "knn.hip", "radius.hip", "rfgrid.hip", "refine.hip", "plane.hip", "verify.hip", "consist.hip", "keypoints.hip", "multiway.hip", "fuse.hip", "clean.hip", "cluster.hip", "disk.hip", "salient.hip"]
 # Kernels whose results must be bit-exact against numpy / torch-CPU arithmetic are compiled without
 # FMA contraction (hipcc defaults to -ffp-contract=fast and __fmul_rn/__fadd_rn are plain operators
 # in this ROCm, so they would fuse); explicit fma()/fmaf() calls are unaffected.
-EXTRA = {"layout.hip": ["-ffp-contract=off"], "match.hip": ["-ffp-contract=off"], "matchf.hip": ["-ffp-contract=off"], "gridnn.hip": ["-ffp-contract=off"], "estim.hip": ["-ffp-contract=off"], "pair.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"], "radius.hip": ["-ffp-contract=off"], "rfgrid.hip": ["-ffp-contract=off"], "refine.hip": ["-ffp-contract=off"], "plane.hip": ["-ffp-contract=off"], "verify.hip": ["-ffp-contract=off"], "consist.hip": ["-ffp-contract=off"], "keypoints.hip": ["-ffp-contract=off"], "multiway.hip": ["-ffp-contract=off"], "fuse.hip": ["-ffp-contract=off"], "clean.hip": ["-ffp-contract=off"], "cluster.hip": ["-ffp-contract=off"], "disk.hip": ["-ffp-contract=off"]}
+EXTRA = {"layout.hip": ["-ffp-contract=off"], "match.hip": ["-ffp-contract=off"], "matchf.hip": ["-ffp-contract=off"], "gridnn.hip": ["-ffp-contract=off"], "estim.hip": ["-ffp-contract=off"], "pair.hip": ["-ffp-contract=off"], "knn.hip": ["-ffp-contract=off"], "radius.hip": ["-ffp-contract=off"], "rfgrid.hip": ["-ffp-contract=off"], "refine.hip": ["-ffp-contract=off"], "plane.hip": ["-ffp-contract=off"], "verify.hip": ["-ffp-contract=off"], "consist.hip": ["-ffp-contract=off"], "keypoints.hip": ["-ffp-contract=off"], "multiway.hip": ["-ffp-contract=off"], "fuse.hip": ["-ffp-contract=off"], "clean.hip": ["-ffp-contract=off"], "cluster.hip": ["-ffp-contract=off"], "disk.hip": ["-ffp-contract=off"], "salient.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-I" + os.path.join(REPO, "include"), "-I" + CSRC]
 if EXPERIMENTS:
@@ -34,7 +34,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(REPO, "include", h) for h in ("yoho_hip.h", "yoho_knn.h", "yoho_trainset.h", "yoho_refine.h", "yoho_plane.h", "yoho_verify.h", "yoho_consist.h", "yoho_keypoints.h", "yoho_multiway.h", "yoho_fuse.h", "yoho_clean.h", "yoho_cluster.h", "yoho_disk.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(REPO, "include", h) for h in ("yoho_hip.h", "yoho_knn.h", "yoho_trainset.h", "yoho_refine.h", "yoho_plane.h", "yoho_verify.h", "yoho_consist.h", "yoho_keypoints.h", "yoho_multiway.h", "yoho_fuse.h", "yoho_clean.h", "yoho_cluster.h", "yoho_disk.h", "yoho_salient.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

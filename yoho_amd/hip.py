@@ -75,6 +75,8 @@ CLUSTER_SYMBOLS = ["yoho_dbscan"]
 DISK_SYMBOLS = ["yoho_disk_sample"]
 DISK_MAX_ROUNDS = 64                        # YOHO_DISK_MAX_ROUNDS
 DISK_DEFAULT_ROUNDS = 16                    # Context.disk_sample's rounds per call (profiles/disk.md: what a scan needs, and the margin)
+# the entries of include/yoho_salient.h (ISS saliency, thinning in the order of a priority), kept apart for the same reason
+SALIENT_SYMBOLS = ["yoho_iss_saliency", "yoho_disk_sample_prio"]
 
 
 class ConvW(C.Structure):
@@ -120,7 +122,7 @@ def load_library():
             f"{_LIB_PATH} not found: build it with `python -m yoho_amd.build` "
             "(there is no CPU fallback for the YOHO hot path)")
     lib = C.CDLL(_LIB_PATH, mode=C.RTLD_GLOBAL)
-    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS + CLUSTER_SYMBOLS + DISK_SYMBOLS:
+    for s in SYMBOLS + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS + CLUSTER_SYMBOLS + DISK_SYMBOLS + SALIENT_SYMBOLS:
         if not hasattr(lib, s):
             raise RuntimeError(f"libyoho_hip.so does not export {s}")
     lib.yoho_last_error.restype = C.c_char_p
@@ -195,7 +197,9 @@ def load_library():
     lib.yoho_statistical_outliers.argtypes = [vp, vp, ci, C.c_float, ci, ci, C.c_double, vp, vp, vp, vp, vp, vp]
     lib.yoho_dbscan.argtypes = [vp, vp, ci, C.c_float, ci, vp, vp, vp, vp, vp, vp]
     lib.yoho_disk_sample.argtypes = [vp, vp, ci, C.c_float, C.c_uint32, ci, ci, vp, vp, vp]
-    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS + CLUSTER_SYMBOLS + DISK_SYMBOLS:
+    lib.yoho_iss_saliency.argtypes = [vp, vp, ci, C.c_float, ci, C.c_double, C.c_double, vp, vp, vp, vp]
+    lib.yoho_disk_sample_prio.argtypes = [vp, vp, ci, C.c_float, vp, C.c_uint32, ci, ci, vp, vp, vp]
+    for s in SYMBOLS[2:] + KNN_SYMBOLS + TRAINSET_SYMBOLS + REFINE_SYMBOLS + PLANE_SYMBOLS + VERIFY_SYMBOLS + CONSIST_SYMBOLS + KEYPOINT_SYMBOLS + MULTIWAY_SYMBOLS + FUSE_SYMBOLS + CLEAN_SYMBOLS + CLUSTER_SYMBOLS + DISK_SYMBOLS + SALIENT_SYMBOLS:
         getattr(lib, s).restype = ci
     _lib = lib
     return lib
@@ -777,6 +781,44 @@ class Context:
         n = torch.empty((3,), dtype=torch.int32, device=pts.device)
         _check(self._lib.yoho_disk_sample(self._h, _dev(pts, torch.float32, "pts"), N, float(radius), int(seed) & 0xFFFFFFFF, int(rounds),
                                           1 if resume else 0, C.c_void_p(state.data_ptr()), C.c_void_p(n.data_ptr()), _stream()))
+        return state, n
+
+    # ---- salient keypoints (include/yoho_salient.h) --------------------------------------------------
+    def iss_saliency(self, pts, radius, min_nbrs=5, gamma21=0.975, gamma32=0.975, want_eig=False):
+        """pts (N,3) f32 -> (prio (N) f32, count (N) int32[, eig (N,3) f64]), device tensors: the eigenvalues l1 <= l2 <= l3 of the f64
+        covariance of the neighbours inside `radius` (the point itself included; count = their number), divided by the count and
+        clamped at 0; prio = l1 where count >= min_nbrs, l2 < gamma21 l3 and l1 < gamma32 l2, NaN elsewhere (yoho_iss_saliency)."""
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError("iss_saliency: pts (N,3)")
+        N = pts.shape[0]
+        prio = torch.empty((N,), dtype=torch.float32, device=pts.device)
+        count = torch.empty((N,), dtype=torch.int32, device=pts.device)
+        eig = torch.empty((N, 3), dtype=torch.float64, device=pts.device) if want_eig else None
+        _check(self._lib.yoho_iss_saliency(self._h, _dev(pts, torch.float32, "pts"), N, float(radius), int(min_nbrs), float(gamma21), float(gamma32),
+                                           C.c_void_p(count.data_ptr()), C.c_void_p(eig.data_ptr()) if want_eig else None,
+                                           C.c_void_p(prio.data_ptr()), _stream()))
+        return (prio, count, eig) if want_eig else (prio, count)
+
+    def disk_sample_prio(self, pts, radius, prio, seed=0, rounds=DISK_DEFAULT_ROUNDS, state=None):
+        """disk_sample in the order of prio (N) f32: higher first, NaN last, equal values in the hashed order of key(i) = mix32(i ^ seed)
+        -> (state (N) uint8, n (3) int32).  state=None starts afresh; a state handed in is continued IN PLACE (and returned): a byte 0
+        is undecided, any other byte is decided and stays - the state of an unfinished call, or the caller's mask, whose rows set to
+        2 are never kept and block nobody (yoho_disk_sample_prio)."""
+        if pts.dim() != 2 or pts.shape[1] != 3:
+            raise ValueError("disk_sample_prio: pts (N,3)")
+        N = pts.shape[0]
+        if prio.dtype != torch.float32 or tuple(prio.shape) != (N,) or prio.device != pts.device:
+            raise ValueError("disk_sample_prio: prio (N) float32 on the device of pts")
+        resume = state is not None
+        if resume:
+            if state.dtype != torch.uint8 or tuple(state.shape) != (N,) or not state.is_contiguous() or state.device != pts.device:
+                raise ValueError("disk_sample_prio: state (N) uint8, contiguous, on the device of pts")
+        else:
+            state = torch.empty((N,), dtype=torch.uint8, device=pts.device)
+        n = torch.empty((3,), dtype=torch.int32, device=pts.device)
+        _check(self._lib.yoho_disk_sample_prio(self._h, _dev(pts, torch.float32, "pts"), N, float(radius), _dev(prio, torch.float32, "prio"),
+                                               int(seed) & 0xFFFFFFFF, int(rounds), 1 if resume else 0, C.c_void_p(state.data_ptr()),
+                                               C.c_void_p(n.data_ptr()), _stream()))
         return state, n
 
     def refit_matches(self, k0, k1, T, inlier_dist, iters=4):

@@ -17,6 +17,13 @@ same kind of coverage in about a dozen parallel rounds; the count then follows f
     kidx, info = keypoints.select_disk(ctx, pc_d, 0.074, voxel=0.025) # no two closer than 0.074, every candidate within 0.074 of one
     r, rows, info = keypoints.disk_radius(ctx, pts, 5000, r0=0.1)     # once per dataset: the radius that keeps about 5000
     yoho_extractor(..., keypoints="disk", keypoint_radius=0.074)
+
+Evenly spread keypoints of an indoor scan lie mostly on walls and floors, where a descriptor says "a plane".  select_salient thins in
+the order of the ISS saliency (include/yoho_salient.h) instead of a hash: non-maximum suppression that goes on to fill
+the gaps:
+
+    kidx, info = keypoints.select_salient(ctx, pc_d, 0.074, voxel=0.025)   # distinctive points first, the rest as select_disk
+    yoho_extractor(..., keypoints="disk", keypoint_radius=0.074, keypoint_saliency={})
 """
 import os
 
@@ -85,14 +92,45 @@ def disk_key(i, seed=0):
     return x ^ (x >> 16)
 
 
-def _thin(ctx, pts, radius, seed, what):
+def prio_ord(prio):
+    """ord of include/yoho_salient.h on an f32 tensor -> int64 in [0, 2^32): the bits, all flipped under a set sign bit, the sign bit
+    set otherwise; every NaN 0"""
+    m = 0xFFFFFFFF
+    b = prio.contiguous().view(torch.int32).to(torch.int64) & m
+    o = torch.where((b >> 31) != 0, ~b & m, b | 0x80000000)
+    return torch.where(torch.isnan(prio), torch.zeros_like(o), o)
+
+
+def prio_key(prio, seed=0):
+    """key64 of include/yoho_salient.h of rows 0 .. N-1 with priorities prio (N) f32 -> (N) int64 holding key64 - 2^63: the order of
+    the signed values is the order of the keys"""
+    hi = ~prio_ord(prio) & 0xFFFFFFFF
+    return ((hi - (1 << 31)) << 32) | disk_key(torch.arange(prio.shape[0], device=prio.device), seed)
+
+
+def _key_order(state, kept, key):
+    """the rows with state 1 in ascending order of key (distinct int64) without another host read (torch.nonzero would be one): one
+    stable sort by the key, one that moves the other rows behind"""
+    order = torch.argsort(key, stable=True)
+    return order[torch.argsort((state[order] != 1).to(torch.uint8), stable=True)][:kept]
+
+
+def _thin(ctx, pts, radius, seed, what, prio=None, state0=None):
     """Context.disk_sample over pts to the end -> (rows kept, in ascending key order; info).  One call and one host read of its
     counts; while rows are undecided, resumed calls - every round decides at least the undecided row of lowest key, so
-    ceil(N / rounds) + 1 calls always suffice and one more is an error, not another turn of a loop."""
+    ceil(N / rounds) + 1 calls always suffice and one more is an error, not another turn of a loop.
+    prio (N) f32 and / or state0 (N) uint8 (left as it is): Context.disk_sample_prio instead - the order of key64
+    (include/yoho_salient.h; prio=None: a constant, the hashed order) from the start state0, whose rows set to 2 are masked out."""
     N = pts.shape[0]
     if N == 0:
         raise ValueError(f"{what}: no candidates")
-    state, n = ctx.disk_sample(pts, radius, seed=seed)
+    if prio is None and state0 is None:
+        step = lambda state: ctx.disk_sample(pts, radius, seed=seed) if state is None else ctx.disk_sample(pts, radius, seed=seed, state=state)      # noqa: E731
+    else:
+        if prio is None:
+            prio = torch.zeros((N,), dtype=torch.float32, device=pts.device)
+        step = lambda state: ctx.disk_sample_prio(pts, radius, prio, seed=seed, state=state)      # noqa: E731
+    state, n = step(None if state0 is None else state0.clone())
     kept, ran, open_ = (int(v) for v in n.tolist())
     if ran < 1 and open_ > 0:
         raise RuntimeError(f"{what}: {open_} rows undecided after a call that ran no round")
@@ -101,13 +139,16 @@ def _thin(ctx, pts, radius, seed, what):
     while open_ > 0:
         if calls >= bound:
             raise RuntimeError(f"{what}: {open_} of {N} rows still undecided after {calls} calls of {ran} rounds")
-        state, n = ctx.disk_sample(pts, radius, seed=seed, state=state)
+        state, n = step(state)
         kept, r, open_ = (int(v) for v in n.tolist())
         calls, rounds = calls + 1, rounds + r
-    # the kept rows in key order without another host read (torch.nonzero would be one): the others sort behind every key, and the
-    # keys are distinct, so any sort gives the one order
-    key = torch.where(state == 1, disk_key(torch.arange(N, device=state.device), seed), torch.full((), 1 << 32, dtype=torch.int64, device=state.device))
-    rows = torch.argsort(key)[:kept]
+    if prio is None:
+        # the kept rows in key order without another host read (torch.nonzero would be one): the others sort behind every key, and the
+        # keys are distinct, so any sort gives the one order
+        key = torch.where(state == 1, disk_key(torch.arange(N, device=state.device), seed), torch.full((), 1 << 32, dtype=torch.int64, device=state.device))
+        rows = torch.argsort(key)[:kept]
+    else:
+        rows = _key_order(state, kept, prio_key(prio, seed))
     return rows, {"radius": float(radius), "kept": kept, "rounds": rounds, "calls": calls, "capped": False}
 
 
@@ -125,6 +166,75 @@ def select_disk(ctx, pc_d, radius, nkpts=None, voxel=None, seed=0, clean=None):
     if clean is not None:
         sel, pts = clean_candidates(ctx, sel, pts, voxel, clean)
     rows, info = _thin(ctx, pts, radius, seed, "select_disk")
+    if nkpts is not None and int(nkpts) < rows.shape[0]:
+        rows = rows[:max(0, int(nkpts))]
+        info["capped"] = True
+    return sel[rows], info
+
+
+SALIENT_MODES = ("greedy", "nms")
+SALIENT_DEFAULT_TIERS = 2                   # rank classes of the response by default: the largest tested number that ends inside one call of 16 rounds (profiles/salient.md)
+
+
+def tier_classes(prio, tiers):
+    """prio (N) f32 with NaN for the ineligible rows -> (N) f32: the rank class tiers - 1 - floor(tiers * descending rank / eligible) of
+    an eligible row (the highest responses in class tiers - 1; equal responses ranked in row order), NaN elsewhere.  On the device,
+    without a host read."""
+    N = prio.shape[0]
+    elig = ~torch.isnan(prio)
+    order = torch.argsort(torch.where(elig, prio, torch.full_like(prio, float("-inf"))), descending=True, stable=True)
+    # the ineligible rows may tie with an eligible -inf: the second stable sort puts every eligible row in front, in the order it has
+    order = order[torch.argsort((~elig[order]).to(torch.uint8), stable=True)]
+    rank = torch.empty((N,), dtype=torch.int64, device=prio.device)
+    rank[order] = torch.arange(N, dtype=torch.int64, device=prio.device)
+    cls = (int(tiers) - 1) - (int(tiers) * rank) // elig.sum().clamp(min=1)
+    return torch.where(elig, cls.to(torch.float32), torch.full_like(prio, float("nan")))
+
+
+def select_salient(ctx, pc_d, radius, salient_radius=None, mode="greedy", fill=True, tiers="default", min_nbrs=5, gamma21=0.975,
+                   gamma32=0.975, nkpts=None, voxel=None, seed=0, clean=None):
+    """Salient keypoints of pc_d (n,3) f64 on the device -> (kidx int64 cloud indices, info): Poisson-disk thinning at `radius` in the
+    order of the ISS saliency (Context.iss_saliency at salient_radius, by default 2 radius) over select_disk's
+    candidates, through clean_candidates when `clean` is a dict.  A row is eligible where its neighbourhood has min_nbrs points and
+    eigenvalues l2 < gamma21 l3, l1 < gamma32 l2; its response is l1.
+    mode "greedy": thinning to the end, the highest response first - non-maximum suppression that goes on to fill the gaps.  fill=True:
+    the ineligible rows follow in hashed order, so select_disk's coverage bound holds for every candidate; fill=False: they are
+    masked out (state 2) and the bound holds among the eligible rows only.
+    mode "nms": ONE round from a start state that masks the ineligible rows, the rows it keeps - classical ISS, the eligible strict
+    local maxima inside `radius`, no fill.
+    tiers=k: the response is replaced by its rank class k - 1 - floor(k * descending rank / eligible) (tier_classes); rows of one
+    class fall in hashed order, which shortens the chains of dependent decisions a smooth response builds.  "default":
+    SALIENT_DEFAULT_TIERS for "greedy", and None - the response itself - for "nms", whose single round builds no chain.
+    kidx is in ascending key64 order (include/yoho_salient.h); nkpts caps it as in select_disk, with the same loss of the bound.
+    info: select_disk's, and eligible, mode, tiers."""
+    if mode not in SALIENT_MODES:
+        raise ValueError(f"select_salient: mode must be one of {SALIENT_MODES}, got {mode!r}")
+    if isinstance(tiers, str):
+        if tiers != "default":
+            raise ValueError(f"select_salient: tiers={tiers!r} must be None, \"default\" or in [1, 2^24]")
+        tiers = SALIENT_DEFAULT_TIERS if mode == "greedy" else None
+    if tiers is not None and not 1 <= int(tiers) <= 1 << 24:
+        raise ValueError(f"select_salient: tiers={tiers!r} must be None, \"default\" or in [1, 2^24]")
+    sel, pts = candidates(ctx, pc_d, voxel)
+    if clean is not None:
+        sel, pts = clean_candidates(ctx, sel, pts, voxel, clean)
+    if pts.shape[0] == 0:
+        raise ValueError("select_salient: no candidates")
+    prio = ctx.iss_saliency(pts, 2.0 * float(radius) if salient_radius is None else float(salient_radius), min_nbrs=min_nbrs, gamma21=gamma21,
+                            gamma32=gamma32)[0]
+    elig = ~torch.isnan(prio)
+    n_elig = elig.sum()
+    if tiers is not None:
+        prio = tier_classes(prio, tiers)
+    masked = torch.where(elig, 0, 2).to(torch.uint8)
+    if mode == "nms":
+        state, n = ctx.disk_sample_prio(pts, radius, prio, seed=seed, rounds=1, state=masked)
+        kept = int(n.tolist()[0])
+        rows = _key_order(state, kept, prio_key(prio, seed))
+        info = {"radius": float(radius), "kept": kept, "rounds": 1, "calls": 1, "capped": False}
+    else:
+        rows, info = _thin(ctx, pts, radius, seed, "select_salient", prio=prio, state0=None if fill else masked)
+    info.update(eligible=int(n_elig.item()), mode=mode, tiers=None if tiers is None else int(tiers))      # read behind the thinning's own host read
     if nkpts is not None and int(nkpts) < rows.shape[0]:
         rows = rows[:max(0, int(nkpts))]
         info["capped"] = True
@@ -172,10 +282,25 @@ def _select_disk_host(ctx, pc, nkpts, voxel, radius, seed, clean=None):
     return select_disk(ctx, pc_d, radius, nkpts=nkpts, voxel=voxel, seed=seed, clean=clean)[0].cpu().numpy()
 
 
+def _select_salient_host(ctx, pc, nkpts, voxel, radius, seed, saliency, clean=None):
+    pc_d = torch.from_numpy(np.ascontiguousarray(np.asarray(pc, dtype=np.float64))).cuda()
+    return select_salient(ctx, pc_d, radius, nkpts=nkpts, voxel=voxel, seed=seed, clean=clean, **saliency)[0].cpu().numpy()
+
+
+def check_saliency(what, name, saliency):
+    """saliency: None, or a dict of select_salient's keyword arguments other than those the caller sets itself -> a copy"""
+    if saliency is None:
+        return None
+    allowed = ("salient_radius", "mode", "fill", "tiers", "min_nbrs", "gamma21", "gamma32")
+    if not isinstance(saliency, dict) or set(saliency) - set(allowed):
+        raise ValueError(f"{what}: {name} must be None or a dict with keys among {allowed}, got {saliency!r}")
+    return dict(saliency)
+
+
 METHODS = ("fps", "disk")
 
 
-def write_keypoints(dataset, nkpts=5000, voxel=0.025, ctx=None, overwrite=False, selector=None, clean=None, method="fps", radius=None, seed=0):
+def write_keypoints(dataset, nkpts=5000, voxel=0.025, ctx=None, overwrite=False, selector=None, clean=None, method="fps", radius=None, seed=0, saliency=None):
     """Spread keypoints for every cloud of an EvalDataset that has no `Keypoints/cloud_bin_{k}Keypoints.txt` yet (overwrite=True: for
     every cloud): the index file, np.savetxt of the cloud indices in pick order, and `Keypoints_PC/cloud_bin_{k}Keypoints.npy`,
     pc[indices] - the two files ThrDMatchPartDataset.get_kps reads, in its formats, so that it never reaches its random draw.  A cloud
@@ -183,14 +308,21 @@ def write_keypoints(dataset, nkpts=5000, voxel=0.025, ctx=None, overwrite=False,
     clean: select's; a selector is then called as selector(pc, nkpts, voxel, clean=clean).
     method: "fps" (select), or "disk" - select_disk at `radius` (required then, refused otherwise) with priority seed `seed`, nkpts
     its cap, the indices in key order; it replaces the default selector only, a selector passed in is called as before.
+    saliency (method "disk" only, refused otherwise): a dict of select_salient's keyword arguments ({}: its defaults) - the thinning
+    runs in the order of the ISS saliency instead of the hash; None: select_disk, as before.
     -> the ids of the clouds written."""
     if method not in METHODS:
         raise ValueError(f"write_keypoints: method must be one of {METHODS}, got {method!r}")
     if (method == "disk") != (radius is not None):
         raise ValueError(f"write_keypoints: method=\"disk\" needs a radius, and only it takes one (method={method!r}, radius={radius!r})")
+    saliency = check_saliency("write_keypoints", "saliency", saliency)
+    if saliency is not None and method != "disk":
+        raise ValueError(f"write_keypoints: saliency orders the thinning of method=\"disk\"; method={method!r} takes none")
     if selector is None:
         ctx = hip.get_context() if ctx is None else ctx
-        if method == "disk":
+        if method == "disk" and saliency is not None:
+            selector = lambda pc, n, v, clean=None: _select_salient_host(ctx, pc, n, v, radius, seed, saliency, clean)      # noqa: E731
+        elif method == "disk":
             selector = lambda pc, n, v, clean=None: _select_disk_host(ctx, pc, n, v, radius, seed, clean)      # noqa: E731
         else:
             selector = lambda pc, n, v, clean=None: _select_host(ctx, pc, n, v, clean)      # noqa: E731

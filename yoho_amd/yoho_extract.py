@@ -69,7 +69,7 @@ KEYPOINT_MODES = ("random", "fps", "disk")
 
 class yoho_extractor():
     def __init__(self, fcgf_ckpt='model/Backbone/best_val_checkpoint.pth', yoho_ckpt='model/PartI_train/model_best.pth',
-                 fcgf=None, so3_dir=None, keypoints="random", keypoint_voxel=None, keypoint_clean=None, keypoint_radius=None, keypoint_seed=0):
+                 fcgf=None, so3_dir=None, keypoints="random", keypoint_voxel=None, keypoint_clean=None, keypoint_radius=None, keypoint_seed=0, keypoint_saliency=None):
         """keypoints: "random" - the reference's np.random.permutation(len(pc))[0:nkpts] on numpy's global generator -, or "fps" -
         farthest-point sampling on the device (yoho_amd.keypoints.select) over the first point of every voxel of
         keypoint_voxel (None: the voxel_size of the call), from candidate 0: no draw from any generator, keypoints in pick order, a
@@ -79,7 +79,9 @@ class yoho_extractor():
         priority seed keypoint_seed (yoho_amd.keypoints.select_disk): no two keypoints closer than the radius, every
         candidate within the radius of one, in about a dozen parallel rounds instead of nkpts dependent picks; the number of
         keypoints follows from the radius (keypoints.disk_radius calibrates it for a dataset) and nkpts only caps it;
-        keypoint_clean is accepted as in "fps"."""
+        keypoint_clean is accepted as in "fps".  keypoint_saliency ("disk" only, refused in the other modes): a dict of
+        yoho_amd.keypoints.select_salient's keyword arguments ({}: its defaults) - the thinning runs in the order of the ISS saliency
+        instead of the hash, distinctive points first; None: select_disk, as before."""
         if keypoints not in KEYPOINT_MODES:
             raise ValueError(f"yoho_extractor: keypoints must be one of {KEYPOINT_MODES}, got {keypoints!r}")
         if keypoint_clean is not None and keypoints not in ("fps", "disk"):
@@ -88,6 +90,10 @@ class yoho_extractor():
             raise ValueError(f"yoho_extractor: keypoints=\"disk\" needs a finite keypoint_radius > 0, got {keypoint_radius!r}")
         if keypoints != "disk" and keypoint_radius is not None:
             raise ValueError(f"yoho_extractor: keypoint_radius is the radius of keypoints=\"disk\"; keypoints={keypoints!r} takes none")
+        keypoint_saliency = KP.check_saliency("yoho_extractor", "keypoint_saliency", keypoint_saliency)
+        if keypoint_saliency is not None and keypoints != "disk":
+            raise ValueError(f"yoho_extractor: keypoint_saliency orders the thinning of keypoints=\"disk\"; keypoints={keypoints!r} takes none")
+        self.keypoint_saliency = keypoint_saliency
         self.keypoints = keypoints
         self.keypoint_radius = None if keypoint_radius is None else float(keypoint_radius)
         self.keypoint_seed = int(keypoint_seed)
@@ -138,6 +144,9 @@ class yoho_extractor():
     def _select(self, ctx, pc_d, voxel_size, nkpts):
         """the device selection of keypoints="fps" / "disk" on the current stream -> cloud indices (k) int64 on the device"""
         voxel = voxel_size if self.keypoint_voxel is None else self.keypoint_voxel
+        if self.keypoints == "disk" and self.keypoint_saliency is not None:
+            return KP.select_salient(ctx, pc_d, self.keypoint_radius, nkpts=nkpts, voxel=voxel, seed=self.keypoint_seed, clean=self.keypoint_clean,
+                                     **self.keypoint_saliency)[0]
         if self.keypoints == "disk":
             return KP.select_disk(ctx, pc_d, self.keypoint_radius, nkpts=nkpts, voxel=voxel, seed=self.keypoint_seed, clean=self.keypoint_clean)[0]
         return KP.select(ctx, pc_d, nkpts, voxel=voxel, clean=self.keypoint_clean)[0]
