@@ -21,7 +21,8 @@ import disk_ref as DR  # noqa: E402
 import keypoints_ref as KR  # noqa: E402
 
 f32, f64 = np.float32, np.float64
-KERNELS = ["dk_zero_kernel", "dk_init_kernel", "dk_round_kernel", "dk_tail_kernel"]
+# dk_init_kernel and dk_round_kernel are templates over the key policy: the hashed key of yoho_disk_sample, the stored key64 of yoho_disk_sample_prio
+KERNELS = {"dk_zero_kernel": 1, "dk_init_kernel": 2, "dk_round_kernel": 2, "dk_tail_kernel": 1}
 OLDER = ("yoho_hip.h", "yoho_knn.h", "yoho_trainset.h", "yoho_refine.h", "yoho_plane.h", "yoho_verify.h", "yoho_consist.h", "yoho_keypoints.h",
          "yoho_multiway.h", "yoho_fuse.h", "yoho_clean.h", "yoho_cluster.h")
 
@@ -57,7 +58,7 @@ def test_library_exports_disk_header_symbol():
     assert 1 <= hip.DISK_DEFAULT_ROUNDS <= hip.DISK_MAX_ROUNDS
     assert build.EXTRA["disk.hip"] == ["-ffp-contract=off"] and "disk.hip" in build.SOURCES
     src = open(os.path.join(build.CSRC, "disk.hip")).read()
-    assert re.findall(r'#include "([^"]+)"', src) == ["rfgrid.h", "yoho_disk.h"]
+    assert re.findall(r'#include "([^"]+)"', src) == ["rfgrid.h", "dkthin.h", "yoho_disk.h", "yoho_salient.h"]
     # the mixer: the constants and the vectors the header gives, against both restatements
     for const in ("0x7feb352d", "0x846ca68b"):
         assert const in hdr and const in src
@@ -69,8 +70,8 @@ def test_library_exports_disk_header_symbol():
 
 
 def test_disk_kernels_use_no_scratch(tmp_path):
-    """csrc/disk.hip compiled for gfx950 with the flags of the build: its four kernels, none with scratch.  The VGPR counts are
-    printed; no bound on them is asserted."""
+    """csrc/disk.hip compiled for gfx950 with the flags of the build: its four kernels, the two templated ones once per key policy,
+    none with scratch.  The VGPR counts are printed; no bound on them is asserted."""
     from yoho_amd import build
     cmd = [build._hipcc()] + build.FLAGS + build.EXTRA["disk.hip"] + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c",
                                                                      os.path.join(build.CSRC, "disk.hip"), "-o", str(tmp_path / "disk.o")]
@@ -79,9 +80,11 @@ def test_disk_kernels_use_no_scratch(tmp_path):
     names = re.findall(r"Function Name: (\S+)", r.stderr)
     scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
     vgprs = [int(x) for x in re.findall(r"\bVGPRs: (\d+)", r.stderr)]
-    assert len(names) == len(scratch) == len(vgprs) == len(KERNELS), names
-    for k in KERNELS:
-        assert sum(k in name for name in names) == 1, (k, names)
+    assert len(names) == len(scratch) == len(vgprs) == sum(KERNELS.values()), names
+    for k, n in KERNELS.items():
+        assert sum(k in name for name in names) == n, (k, names)
+    for k in ("dk_init_kernel", "dk_round_kernel"):
+        assert sorted(p for name in names if k in name for p in ("DkHashed", "DkStored") if p in name) == ["DkHashed", "DkStored"], names
     print("disk.hip: " + ", ".join(f"{n} {v} VGPRs" for n, v in zip(names, vgprs)))
     assert scratch == [0] * len(names), dict(zip(names, scratch))
 

@@ -21,7 +21,7 @@ import keypoints_ref as KR  # noqa: E402
 import salient_ref as SR  # noqa: E402
 
 f32, f64 = np.float32, np.float64
-KERNELS = ["sl_saliency_kernel", "sp_zero_kernel", "sp_init_kernel", "sp_round_kernel", "sp_tail_kernel"]
+KERNELS = ["sl_saliency_kernel"]
 OLDER = ("yoho_hip.h", "yoho_knn.h", "yoho_trainset.h", "yoho_refine.h", "yoho_plane.h", "yoho_verify.h", "yoho_consist.h", "yoho_keypoints.h",
          "yoho_multiway.h", "yoho_fuse.h", "yoho_clean.h", "yoho_cluster.h", "yoho_disk.h")
 CLOUDS = [(300, 0.15, 0), (1500, 0.09, 1), (1500, 0.2, 7)]
@@ -57,8 +57,9 @@ def test_library_exports_salient_header_symbols():
     assert int(re.search(r"#define\s+YOHO_SALIENT_MAX_ROUNDS\s+(\d+)", hdr).group(1)) == hip.DISK_MAX_ROUNDS == SR.MAX_ROUNDS
     assert build.EXTRA["salient.hip"] == ["-ffp-contract=off"] and "salient.hip" in build.SOURCES
     src = open(os.path.join(build.CSRC, "salient.hip")).read()
-    assert re.findall(r'#include "([^"]+)"', src) == ["rfgrid.h", "yoho_salient.h"]
-    assert "plane.hip" in src.split("#include")[0] and "disk.hip" in src.split("#include")[0]         # the head comment says what is restated
+    assert re.findall(r'#include "([^"]+)"', src) == ["rfgrid.h", "rffit.h", "dkthin.h", "yoho_salient.h"]
+    for shared in ("_round_kernel", "_tail_kernel", "_zero_kernel", "0x1p-58", "0x7feb352d", "0x846ca68b"):      # the thinning is disk.hip's, the Jacobi rffit.h's
+        assert shared not in src, shared
     vectors = re.findall(r"\((\d+), (\d+), (0x[0-9a-f]{8})\) -> (0x[0-9a-f]{16})", hdr)
     assert len(vectors) >= 3 and {((int(i), int(s), int(p, 16)), int(k, 16)) for i, s, p, k in vectors} == set(SR.HEADER_VECTORS)
     for (i, s, bits), k in SR.HEADER_VECTORS:
@@ -75,8 +76,8 @@ def test_library_exports_salient_header_symbols():
 
 
 def test_salient_kernels_use_no_scratch(tmp_path):
-    """csrc/salient.hip compiled for gfx950 with the flags of the build: its five kernels, none with scratch.  The VGPR counts are
-    printed; no bound on them is asserted."""
+    """csrc/salient.hip compiled for gfx950 with the flags of the build: its one kernel (the thinning kernels are disk.hip's,
+    tests/test_disk_cpu.py), without scratch.  The VGPR count is printed; no bound on it is asserted."""
     from yoho_amd import build
     cmd = [build._hipcc()] + build.FLAGS + build.EXTRA["salient.hip"] + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c",
                                                                         os.path.join(build.CSRC, "salient.hip"), "-o", str(tmp_path / "salient.o")]
@@ -90,6 +91,28 @@ def test_salient_kernels_use_no_scratch(tmp_path):
         assert sum(k in name for name in names) == 1, (k, names)
     print("salient.hip: " + ", ".join(f"{n} {v} VGPRs" for n, v in zip(names, vgprs)))
     assert scratch == [0] * len(names), dict(zip(names, scratch))
+
+
+def test_the_grid_family_shares_its_pieces():
+    """each piece the entries on the cell-sorted grid share is written once: the bucket hash in rfgrid.h (gridnn.hip's grid is the
+    one it was copied from; fourier.hip's sample hash and sparse.h's voxel hash use the same multiplier for other things and are
+    listed, so a fifth file fails), the Jacobi's skip rule in rffit.h, the mixer in disk.hip; the names of the copies are gone.  The
+    sparse backbone's helpers are sp_* as well, so that prefix is looked for outside its files (sp*.hip, sp*.h)."""
+    from yoho_amd import build
+    files = {f: open(os.path.join(build.CSRC, f)).read() for f in sorted(os.listdir(build.CSRC)) if f.endswith((".hip", ".h"))}
+    where = lambda text: sorted(f for f, src in files.items() if text in src)      # noqa: E731
+    assert where("0x9E3779B97F4A7C15") == ["fourier.hip", "gridnn.hip", "rfgrid.h", "sparse.h"]
+    family = [f for f, src in files.items() if '#include "rfgrid.h"' in src]
+    assert {"clean.hip", "cluster.hip", "disk.hip", "salient.hip", "plane.hip", "refine.hip", "verify.hip", "multiway.hip", "fuse.hip", "rfgrid.hip"} <= set(family)
+    assert not [f for f in family if "0x9E3779B97F4A7C15" in files[f]]
+    assert where("0x1p-58") == ["rffit.h"]
+    assert where("0x7feb352d") == ["disk.hip"]
+    for gone in ("cu_walk", "pl_eig3", "sl_eig3", "cu_load_row", "CL_SEEN", "CU_SEEN"):
+        assert where(gone) == [], gone
+    assert [f for f in where("sp_") if not f.startswith("sp")] == []
+    # one walk over the distinct buckets and one Jacobi, each with the callers it had as copies
+    assert where("rf_walk_each(") == ["clean.hip", "cluster.hip", "rfgrid.h"] and where("rf_moments(") == ["plane.hip", "rfgrid.h", "salient.hip"]
+    assert where("rf_eig3<") == ["plane.hip", "salient.hip"] and where("dk_thin(") == ["disk.hip", "dkthin.h", "salient.hip"]
 
 
 # ---- the restatements ----------------------------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 
     python tools/time_clean.py [--sizes 20000,100000,300000] [--rounds 5] [--out FILE]
     python tools/time_clean.py --resources           # the compiler's report on csrc/clean.hip: needs no GPU
+    python tools/time_clean.py --lib other/libyoho_hip.so      # the same windows on another build of the library
 
 One process, inputs resident on the device, every variant warmed twice, device events around a window of calls that lasts at least
 `--window` seconds, the variants of a size taking turns `--rounds` times; median and [min, max] of the per-call times."""
@@ -94,6 +95,7 @@ def main():
     ap.add_argument("--window", type=float, default=0.1)
     ap.add_argument("--resources", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="load this build of libyoho_hip.so instead of the tree's")
     args = ap.parse_args()
     if args.resources:
         print("\n".join(resources()))
@@ -102,8 +104,10 @@ def main():
     from yoho_amd import hip, synth
     if not torch.cuda.is_available():
         raise SystemExit("time_clean.py measures on the GPU; there is none here")
+    if args.lib:
+        hip._LIB_PATH = os.path.abspath(args.lib)
     c = hip.get_context()
-    lines = [f"device: {torch.cuda.get_device_name(0)}", "",
+    lines = [f"device: {torch.cuda.get_device_name(0)}; library {hip._LIB_PATH if args.lib else 'of the tree'}", "",
              f"k = {K}, max_dist = 4 sqrt(area / N); ms per call: median [min, max] of {args.rounds} alternated windows of >= {args.window} s (calls per window)", "",
              "| N | max_dist m | neighbours inside: median / max | kept | variant | ms per call | calls |", "|---|---|---|---|---|---|---|"]
     cell = lambda r: f"{r[0]:.3f} [{r[1]:.3f}, {r[2]:.3f}] | {r[3]}"       # noqa: E731

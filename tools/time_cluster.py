@@ -7,6 +7,7 @@
 
     python tools/time_cluster.py [--sizes 20000,100000,300000] [--rounds 5] [--out FILE]
     python tools/time_cluster.py --resources         # the compiler's report on csrc/cluster.hip: needs no GPU
+    python tools/time_cluster.py --lib other/libyoho_hip.so      # the same windows on another build of the library
     python tools/time_cluster.py --once N            # one warmed call of each at one size and nothing else: for a kernel trace
 
 The protocol is tools/time_clean.py's: one process, inputs resident on the device, every variant warmed twice, device events around a
@@ -53,6 +54,7 @@ def main():
     ap.add_argument("--resources", action="store_true")
     ap.add_argument("--once", type=int, default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="load this build of libyoho_hip.so instead of the tree's")
     args = ap.parse_args()
     if args.resources:
         print("\n".join(resources()))
@@ -61,6 +63,8 @@ def main():
     from yoho_amd import hip
     if not torch.cuda.is_available():
         raise SystemExit("time_cluster.py measures on the GPU; there is none here")
+    if args.lib:
+        hip._LIB_PATH = os.path.abspath(args.lib)
     c = hip.get_context()
     if args.once is not None:
         p, r = cloud(torch, args.once)
@@ -69,7 +73,7 @@ def main():
             c.knn_within(p, p, r, 1, skip_same_row=True, want_idx=False, want_d2=False)
         torch.cuda.synchronize()
         return
-    lines = [f"device: {torch.cuda.get_device_name(0)}", "",
+    lines = [f"device: {torch.cuda.get_device_name(0)}; library {hip._LIB_PATH if args.lib else 'of the tree'}", "",
              f"min_pts = {MIN_PTS}, eps = 4 sqrt(area / N); ms per call: median [min, max] of {args.rounds} alternated windows of >= {args.window} s (calls per window)", "",
              "| N | eps m | neighbours inside: median / max | clusters / core rows / noise rows | variant | ms per call | calls |", "|---|---|---|---|---|---|---|"]
     cell = lambda r: f"{r[0]:.3f} [{r[1]:.3f}, {r[2]:.3f}] | {r[3]}"       # noqa: E731

@@ -11,6 +11,7 @@
 
     python tools/time_disk.py [--part entry|extractor|all] [--out FILE]
     python tools/time_disk.py --part extractor --modes random --repo OTHER_CHECKOUT      # the same leg of another (built) checkout
+    python tools/time_disk.py --part entry --lib other/libyoho_hip.so                    # this tree's Python over another build of the library
 
 The last form is how the parent commit's figures are taken on the same box, in processes of its own before and between."""
 import argparse
@@ -110,6 +111,7 @@ def main():
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--repo", default=None, help="import yoho_amd from this (built) checkout instead of the one the tool lies in")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="load this build of libyoho_hip.so instead of the tree's")
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.repo) if args.repo else os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch
@@ -117,7 +119,9 @@ def main():
     from yoho_amd import weights as W
     if not torch.cuda.is_available():
         raise SystemExit("time_disk.py measures on the GPU; there is none here")
-    lines = [f"device: {torch.cuda.get_device_name(0)}"]
+    if args.lib:
+        hip._LIB_PATH = os.path.abspath(args.lib)
+    lines = [f"device: {torch.cuda.get_device_name(0)}; library {hip._LIB_PATH if args.lib else 'of the tree'}"]
     if args.part in ("entry", "all"):
         entry(torch, hip, synth, args, lines)
     if args.part in ("extractor", "all"):

@@ -5,6 +5,7 @@
       tol < 0 (every iteration is made), per call and per iteration, alternated in one process.
 
     python tools/time_plane.py [--repeats 10] [--iters 30] [--out FILE]        # the tables it prints go into profiles/plane_icp.md
+    python tools/time_plane.py --lib other/libyoho_hip.so                      # the same on another build of the library
 
 The inputs are the tests' own (tests/refine_ref.py icp_case; the large pair is tools/time_refine.py's).  Host clock around work that
 ends in a device synchronise; every variant warmed twice; the variants alternate `--repeats` times; median and [min, max]."""
@@ -38,11 +39,14 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--sizes", type=int, nargs="*", default=[20000, 300000])
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="load this build of libyoho_hip.so instead of the tree's")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_plane.py measures on the GPU; there is none here")
+    if args.lib:
+        hip._LIB_PATH = os.path.abspath(args.lib)
     c = hip.get_context()
-    lines = [f"device: {torch.cuda.get_device_name(0)}"]
+    lines = [f"device: {torch.cuda.get_device_name(0)}; library {hip._LIB_PATH if args.lib else 'of the tree'}"]
     for n in args.sizes:
         ic, radius = pair_of(n)
         src, tgt, T0, md, gt = cu(ic["src"]), cu(ic["tgt"]), cu(ic["T0"]), ic["max_dist"], ic["T_gt"]

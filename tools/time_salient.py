@@ -12,6 +12,7 @@ of calls with host reads between them, so it is timed by a host clock around wor
               at radius 0.074, without keypoint_saliency, with {} and with {"tiers": None}, alternating
 
     python tools/time_salient.py [--part registers|saliency|thin|extractor|all] [--out FILE]
+    python tools/time_salient.py --part thin --lib other/libyoho_hip.so      # the same part on another build of the library
 
 Every part (for saliency and thin: every cloud size) runs in a child process of its own under its own time limit, so a step that
 hangs ends there and the parts behind it are not started."""
@@ -44,12 +45,14 @@ def cloud_and_radius(torch, c, synth, m):
 
 def registers(args):
     from yoho_amd import build
-    cmd = [build._hipcc()] + build.FLAGS + build.EXTRA["salient.hip"] + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c",
-                                                                        os.path.join(build.CSRC, "salient.hip"), "-o", os.devnull]
-    err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    names = re.findall(r"Function Name: \w*?(s[lp]_\w+_kernel)", err)
+    err = ""
+    for src in ("salient.hip", "disk.hip"):              # the saliency kernel, and the thinning kernels of both entries (K = DkHashed, DkStored)
+        cmd = [build._hipcc()] + build.FLAGS + build.EXTRA[src] + ["-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c",
+                                                                  os.path.join(build.CSRC, src), "-o", os.devnull]
+        err += subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+    names = [m[0] + (f"<{m[1]}>" if m[1] else "") for m in re.findall(r"Function Name: \w*?((?:sl|dk)_\w+?_kernel)(?:I\w*?\d+(Dk\w+?)E)?\w*", err)]
     cols = [re.findall(rf"{k}: (\d+)", err) for k in (r"\bVGPRs", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]")]
-    lines = ["", "csrc/salient.hip, hipcc -O3 -ffp-contract=off, gfx950", "", "| kernel | VGPRs | scratch bytes per lane | waves per SIMD |", "|---|---|---|---|"]
+    lines = ["", "csrc/salient.hip and csrc/disk.hip, hipcc -O3 -ffp-contract=off, gfx950", "", "| kernel | VGPRs | scratch bytes per lane | waves per SIMD |", "|---|---|---|---|"]
     return lines + [f"| {n} | {v} | {s} | {o} |" for n, v, s, o in zip(names, *cols)]
 
 
@@ -129,6 +132,8 @@ STEPS = {"registers": registers, "saliency": saliency, "thin": thin, "extractor"
 def child(step, m, args):
     """one step in a process of its own under its time limit -> its lines; raises when it fails or runs out of time"""
     cmd = [sys.executable, os.path.abspath(__file__), "--step", step, "--m", str(m), "--repeats", str(args.repeats), "--runs", str(args.runs)]
+    if args.lib:
+        cmd += ["--lib", args.lib]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=LIMITS[step])
     if r.returncode != 0:
         raise SystemExit(f"time_salient.py: step {step} (m = {m}) failed with {r.returncode}; nothing more is started\n{r.stderr[-3000:]}")
@@ -143,13 +148,17 @@ def main():
     ap.add_argument("--repeats", type=int, default=4)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="load this build of libyoho_hip.so instead of the tree's")
     args = ap.parse_args()
+    if args.lib:
+        from yoho_amd import hip
+        hip._LIB_PATH = args.lib = os.path.abspath(args.lib)
     if args.step:
         for ln in STEPS[args.step](args):
             print("> " + ln)
         return
     parts = tuple(STEPS) if args.part == "all" else (args.part,)
-    lines = []
+    lines = [f"library: {args.lib or 'of the tree'}"]
     if "registers" in parts:
         lines += child("registers", 0, args)
     if "saliency" in parts:

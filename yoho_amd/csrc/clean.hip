@@ -9,13 +9,8 @@
 //   cl_thr_kernel          one wave: sigma, thr
 //   cl_keep_kernel         keep[i], n_keep
 //
-// THE WALK.  The 27 cells around a query hold every candidate (rfgrid.hip (1) - (3)).  rf_walk may meet a point twice - clamped
-// neighbour cells are the same cell, and two of the 27 can hash to one bucket -, which a minimum does not notice and a count or a list
-// does.  So, as in pl_normals_kernel, the 27 slots are computed first, in registers, and a slot equal to an earlier one is marked:
-// every bucket is walked once, every point of it goes through the exact f32 test, a point lies in one bucket only, and the count
-// is exact.  Unlike there, the marked slots are then parked in LDS, one column per lane, and the buckets are walked by a loop that is not
-// unrolled: the body holds the insertion chain below, and 27 copies of a 31-step chain would not fit the instruction cache.  A lane
-// reads its own column only, so no barrier is needed.
+// THE WALK is rfgrid.h's rf_walk_each (THE DISTINCT BUCKETS): every bucket of the 27 cells around a query is walked once, so the count
+// is exact, and the loop over the buckets is not unrolled, because the functor here holds the insertion chain below.
 //
 // THE LIST.  The k best are packed keys nn_key(d2 bits, j) (nnmath.h), kept sorted ascending in CAP registers; d2 >= +0, so the order of the
 // integers is the contract's order of (d2, j) - matchf.hip's packing.  An empty place holds NN_KEY_EMPTY, all ones, above every key
@@ -38,7 +33,6 @@
 
 namespace yoho {
 
-constexpr unsigned CL_SEEN = 0xFFFFFFFFu;      // no slot: a slot is below 2^23
 constexpr int CL_SLAB = 2;                     // doubles per slab row
 
 template <int CAP>
@@ -58,40 +52,15 @@ __device__ __forceinline__ void cl_insert(u64 (&key)[CAP], u64 cand) {
 // the candidates of q among the grid's points, row `self` left out (-1: none): their number; CAP > 0: the CAP smallest keys, ascending
 template <int CAP>
 __device__ __forceinline__ int cl_walk(const RfGrid& g, const float (&q)[3], int self, u64 (&key)[CAP > 0 ? CAP : 1], unsigned (*slots)[256]) {
-    const int cx = rf_cell((double)q[0], g.inv_cell), cy = rf_cell((double)q[1], g.inv_cell), cz = rf_cell((double)q[2], g.inv_cell);
-    {
-        unsigned slot[27];
-#pragma unroll
-        for (int c = 0; c < 27; ++c) slot[c] = rf_slot(rf_clampi(cx + c % 3 - 1), rf_clampi(cy + (c / 3) % 3 - 1), rf_clampi(cz + c / 9 - 1), g.mask);
-#pragma unroll
-        for (int c = 0; c < 27; ++c) {
-            bool seen = false;
-#pragma unroll
-            for (int k = 0; k < c; ++k) seen = seen || slot[k] == slot[c];
-            slots[c][threadIdx.x] = seen ? CL_SEEN : slot[c];             // a bucket is walked once
-        }
-    }
     if constexpr (CAP > 0) {
 #pragma unroll
         for (int m = 0; m < CAP; ++m) key[m] = NN_KEY_EMPTY;
     }
     int n = 0;
-#pragma unroll 1
-    for (int c = 0; c < 27; ++c) {
-        const unsigned s = slots[c][threadIdx.x];
-        if (s == CL_SEEN) continue;
-        const int p1 = g.start[s + 1];
-        for (int p = g.start[s]; p < p1; ++p) {
-            const float4 v = g.pk[p];
-            const float b[3] = {v.x, v.y, v.z};
-            const float d2 = dist2_f32<3>(q, b);
-            const int j = __float_as_int(v.w);
-            if (d2 < g.gate2 && j != self) {                              // false for a NaN / inf on either side
-                ++n;
-                if constexpr (CAP > 0) cl_insert<CAP>(key, nn_key(__float_as_uint(d2), (unsigned)j));
-            }
-        }
-    }
+    rf_walk_each(g, q, self, slots, [&](float d2, int j) {
+        ++n;
+        if constexpr (CAP > 0) cl_insert<CAP>(key, nn_key(__float_as_uint(d2), (unsigned)j));
+    });
     return n;
 }
 
@@ -101,7 +70,8 @@ __global__ __launch_bounds__(256) void cl_knn_kernel(RfGrid g, const float* __re
     __shared__ unsigned slots[27][256];
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Nq) return;                                                  // no barrier below
-    const float qq[3] = {q[3 * (size_t)i], q[3 * (size_t)i + 1], q[3 * (size_t)i + 2]};
+    float qq[3];
+    rf_load_row(q, i, qq);
     u64 key[CAP > 0 ? CAP : 1];
     const int n = cl_walk<CAP>(g, qq, skip ? i : -1, key, slots);
     if (count) count[i] = n;
@@ -125,7 +95,8 @@ __global__ __launch_bounds__(256) void cl_stat_kernel(RfGrid g, const float* __r
     const int i = blockIdx.x * 256 + threadIdx.x;
     double v[2] = {0.0, 0.0};
     if (i < N) {
-        const float qq[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
+        float qq[3];
+        rf_load_row(pts, i, qq);
         u64 key[CAP];
         const int n = cl_walk<CAP>(g, qq, i, key, slots);
         const int found = n < k ? n : k;
@@ -231,8 +202,7 @@ int yoho_statistical_outliers(yoho_ctx* c, const float* pts, int N, float max_di
                               int32_t* count, uint8_t* keep, double* stats, int32_t* n_keep, void* stream) {
     const char* fn = "yoho_statistical_outliers";
     int rc;
-    if ((rc = rf_check_sizes(fn, c, "N", N, 1)) || (rc = rf_check_limit(fn, RF_NAMED(YOHO_REFINE_MAX_POINTS), "N", N)) ||
-        (rc = rf_check_radius(fn, "max_dist", max_dist)) || (rc = cl_check_k(fn, k))) return rc;
+    if ((rc = rf_check_cloud(fn, c, N, "max_dist", max_dist)) || (rc = cl_check_k(fn, k))) return rc;
     if (min_found < 1) { set_error("yoho_statistical_outliers: min_found=%d must be at least 1", min_found); return YOHO_EINVAL; }
     if (std::isnan(std_ratio)) { set_error("yoho_statistical_outliers: std_ratio is NaN"); return YOHO_EINVAL; }
     if ((rc = rf_check_pointers(fn, pts && keep && stats && n_keep))) return rc;

@@ -8,12 +8,8 @@
 //   cu_scan_kernel      one workgroup: the exclusive scan of the block counts, n_out = {C, 0, 0}
 //   cu_label_kernel     labels[i] = rank of root[i] among the roots in row order; sizes and n_out[1..2] by integer atomics
 //
-// THE WALK is clean.hip's, restated here because that file's include list and kernel census are pinned by its tests: the 27 slots
-// around a row are computed first, a slot equal to an earlier one is marked, the marked slots are parked in LDS, one column per lane
-// (a lane reads its own column only: no barrier), and every distinct bucket is walked once, so a count is exact (rf_walk may meet a
-// point twice, which a minimum does not notice and a count does).  Here it is one device function, cu_walk, that hands every
-// candidate (d2 < gate2, j != self) to a functor: the three passes differ in the functor alone.  A later refactor may unify the two
-// files' walks.
+// THE WALK is rfgrid.h's rf_walk_each (THE DISTINCT BUCKETS), which hands every candidate (d2 < gate2, j != self) to a functor once:
+// the three passes differ in the functor alone.
 //
 // THE UNION.  parent[] is a forest with parent[x] <= x, every row its own root after cu_count_kernel.  A lane of cu_union_kernel
 // finds the roots of both ends of an edge and hooks the LARGER root under the smaller with a compare-and-swap that expects the larger
@@ -47,45 +43,6 @@
 
 namespace yoho {
 
-constexpr unsigned CU_SEEN = 0xFFFFFFFFu;      // no slot: a slot is below 2^23
-
-// every candidate of q among the grid's points, row `self` left out: f(d2, j), each once, in no promised order
-template <typename F>
-__device__ __forceinline__ void cu_walk(const RfGrid& g, const float (&q)[3], int self, unsigned (*slots)[256], F&& f) {
-    const int cx = rf_cell((double)q[0], g.inv_cell), cy = rf_cell((double)q[1], g.inv_cell), cz = rf_cell((double)q[2], g.inv_cell);
-    {
-        unsigned slot[27];
-#pragma unroll
-        for (int c = 0; c < 27; ++c) slot[c] = rf_slot(rf_clampi(cx + c % 3 - 1), rf_clampi(cy + (c / 3) % 3 - 1), rf_clampi(cz + c / 9 - 1), g.mask);
-#pragma unroll
-        for (int c = 0; c < 27; ++c) {
-            bool seen = false;
-#pragma unroll
-            for (int k = 0; k < c; ++k) seen = seen || slot[k] == slot[c];
-            slots[c][threadIdx.x] = seen ? CU_SEEN : slot[c];             // a bucket is walked once
-        }
-    }
-#pragma unroll 1
-    for (int c = 0; c < 27; ++c) {
-        const unsigned s = slots[c][threadIdx.x];
-        if (s == CU_SEEN) continue;
-        const int p1 = g.start[s + 1];
-        for (int p = g.start[s]; p < p1; ++p) {
-            const float4 v = g.pk[p];
-            const float b[3] = {v.x, v.y, v.z};
-            const float d2 = dist2_f32<3>(q, b);
-            const int j = __float_as_int(v.w);
-            if (d2 < g.gate2 && j != self) f(d2, j);                      // false for a NaN / inf on either side
-        }
-    }
-}
-
-__device__ __forceinline__ void cu_load_row(const float* __restrict__ pts, int i, float (&q)[3]) {
-    q[0] = pts[3 * (size_t)i];
-    q[1] = pts[3 * (size_t)i + 1];
-    q[2] = pts[3 * (size_t)i + 2];
-}
-
 __global__ __launch_bounds__(256) void cu_count_kernel(RfGrid g, const float* __restrict__ pts, int N, int min_pts, int32_t* __restrict__ count,
                                                        uint8_t* __restrict__ core, uint8_t* __restrict__ cw, int* __restrict__ parent,
                                                        int32_t* __restrict__ sizes) {
@@ -93,11 +50,10 @@ __global__ __launch_bounds__(256) void cu_count_kernel(RfGrid g, const float* __
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;                                                   // no barrier below
     float q[3];
-    cu_load_row(pts, i, q);
+    rf_load_row(pts, i, q);
     int n = 0;
-    cu_walk(g, q, i, slots, [&](float, int) { ++n; });
-    const bool finite = fabsf(q[0]) < __builtin_inff() && fabsf(q[1]) < __builtin_inff() && fabsf(q[2]) < __builtin_inff();
-    const uint8_t c = finite && n >= min_pts - 1 ? 1 : 0;                 // count + 1 >= min_pts, min_pts >= 1
+    rf_walk_each(g, q, i, slots, [&](float, int) { ++n; });
+    const uint8_t c = rf_finite3(q[0], q[1], q[2]) && n >= min_pts - 1 ? 1 : 0;     // count + 1 >= min_pts, min_pts >= 1
     if (count) count[i] = n;
     if (core) core[i] = c;
     cw[i] = c;
@@ -160,9 +116,9 @@ __global__ __launch_bounds__(256) void cu_union_kernel(RfGrid g, const float* __
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N || !cw[i]) return;                                         // no barrier below
     float q[3];
-    cu_load_row(pts, i, q);
+    rf_load_row(pts, i, q);
     int ri = i;                                                           // an ancestor of i: where the last edge left it
-    cu_walk(g, q, i, slots, [&](float, int j) {
+    rf_walk_each(g, q, i, slots, [&](float, int j) {
         if (j < i && cw[j]) ri = cu_edge(parent, ri, j);                  // the edge {i, j} once, from its higher end
     });
 }
@@ -190,9 +146,9 @@ __global__ __launch_bounds__(256) void cu_root_kernel(RfGrid g, const float* __r
             is_root = r == i;
         } else {
             float q[3];
-            cu_load_row(pts, i, q);
+            rf_load_row(pts, i, q);
             u64 best = NN_KEY_EMPTY;
-            cu_walk(g, q, i, slots, [&](float d2, int j) {
+            rf_walk_each(g, q, i, slots, [&](float d2, int j) {
                 const u64 key = nn_key(__float_as_uint(d2), (unsigned)j);       // d2 >= +0: the order of the integers is that of (d2, j)
                 if (cw[j] && key < best) best = key;
             });
@@ -274,8 +230,7 @@ int yoho_dbscan(yoho_ctx* c, const float* pts, int N, float eps, int min_pts, in
                 int32_t* n_out, void* stream) {
     const char* fn = "yoho_dbscan";
     int rc;
-    if ((rc = rf_check_sizes(fn, c, "N", N, 1)) || (rc = rf_check_limit(fn, RF_NAMED(YOHO_REFINE_MAX_POINTS), "N", N)) ||
-        (rc = rf_check_radius(fn, "eps", eps)) || (rc = rf_check_range(fn, "min_pts", min_pts, 1, RF_NAMED(INT_MAX)))) return rc;
+    if ((rc = rf_check_cloud(fn, c, N, "eps", eps)) || (rc = rf_check_range(fn, "min_pts", min_pts, 1, RF_NAMED(INT_MAX)))) return rc;
     if (!pts) return RF_REFUSE("%s: bad argument (pts is NULL)", fn);
     if (!labels) return RF_REFUSE("%s: bad argument (labels is NULL)", fn);
     if (!n_out) return RF_REFUSE("%s: bad argument (n_out is NULL)", fn);

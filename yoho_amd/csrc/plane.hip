@@ -1,6 +1,6 @@
 // Surface normals and point-to-plane ICP (include/yoho_plane.h).  Compiled with -ffp-contract=off like refine.hip (yoho_amd/build.py).
-// The cell-sorted grid and its walk come from rfgrid.hip / rfgrid.h (THE GRID, THE QUERY's exactness argument), the fixed-order f64
-// sums and the rounded transform from rffit.h (THE SUMS, rf_apply); both carry over unchanged.
+// The cell-sorted grid and its walks come from rfgrid.hip / rfgrid.h (THE GRID, THE QUERY's exactness argument), the fixed-order f64
+// sums, the rounded transform and the Jacobi from rffit.h (THE SUMS, rf_apply, rf_eig3).
 //
 //   pl_normals_kernel      yoho_estimate_normals: one lane per point over the 27 cells around it, ten accumulators, a 3 x 3 Jacobi
 //   pl_pair_kernel         ICP: transform + rf_walk + the normal test + first-pass partial sums {n, SUM x}
@@ -9,13 +9,9 @@
 //   pl_solve_kernel        one wave: rmse, the 6 x 6 Cholesky solve, exp([w]x), the update and the stop word
 //
 // THE NORMALS.  The grid is built over the points themselves with cell side radius (1 + 2^-10), so the 27 cells around a point hold
-// every j with d2 < gate2 (rfgrid.hip (1) - (3), with the point as the query).  A count needs more than the nearest-neighbour walk
-// does: there a point met twice changes nothing, here it would be counted twice.  Two of the 27 cells can share a bucket - clamped
-// neighbour cells are the same cell, and different cells can hash to one slot - so the 27 slots are computed first and a slot equal
-// to an earlier one is skipped: every bucket is walked once, every point of it goes through the exact f32 test, and count is exact.
-// One lane per point, not a wave: the ten accumulators (n, S1 (3), S2 (6)) stay in registers with no cross-lane sum, whose order
-// would have to be fixed as well; the f64 adds are a dozen per neighbour behind a 16-byte load each, and neighbouring lanes walk
-// neighbouring cells.  A wave per point would pay 60 butterfly steps of f64 per point for ~30 neighbours.
+// every j with d2 < gate2 (rfgrid.hip (1) - (3), with the point as the query).  The count and the ten sums are rfgrid.h's rf_moments
+// (THE DISTINCT BUCKETS: a count needs every bucket walked once), the eigenvectors rffit.h's rf_eig3; what is this file's is the
+// choice of the normal, its sign and the curvature.
 //
 // THE ITERATIONS are queued at once, four launches each, with refine.hip's state machine: PlState lives in the workspace, a kernel
 // that finds the stop word set returns at once - a wave-uniform branch on a loaded word.  x_e is recomputed by the second pass (the
@@ -38,81 +34,24 @@ constexpr double PL_PIVOT_TOL = 1e-13;
 constexpr double PL_COLLINEAR_TOL = 1e-12;
 
 // ---- normals -----------------------------------------------------------------------------------------------------------------------
-// symmetric 3 x 3 (a = {xx, xy, xz, yy, yz, zz}) -> eigenvalues lam[3] (unsorted) and eigenvectors as the columns of V (row-major):
-// cyclic two-sided Jacobi.  A rotation is skipped once the off-diagonal entry is below 2^-58 of the two diagonal entries it couples: an
-// absolute perturbation that small turns an eigenvector by 2^-58 / (relative gap), far inside the bound of tests/test_gpu_plane.py.
-__device__ void pl_eig3(const double (&a)[6], double (&lam)[3], double (&V)[9]) {
-    double A[3][3] = {{a[0], a[1], a[2]}, {a[1], a[3], a[4]}, {a[2], a[4], a[5]}};
-#pragma unroll
-    for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        bool rotated = false;
-#pragma unroll
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2, r = 3 - p - q;
-            const double apq = A[p][q];
-            if (fabs(apq) > 0x1p-58 * (fabs(A[p][p]) + fabs(A[q][q]))) {
-                rotated = true;
-                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
-                const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
-                A[p][p] -= t * apq;
-                A[q][q] += t * apq;
-                A[p][q] = A[q][p] = 0.0;
-                const double arp = A[r][p], arq = A[r][q];
-                A[r][p] = A[p][r] = cs * arp - sn * arq;
-                A[r][q] = A[q][r] = sn * arp + cs * arq;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const double vp = V[k * 3 + p], vq = V[k * 3 + q];
-                    V[k * 3 + p] = cs * vp - sn * vq;
-                    V[k * 3 + q] = sn * vp + cs * vq;
-                }
-            }
-        }
-        if (!rotated) break;
-    }
-    lam[0] = A[0][0]; lam[1] = A[1][1]; lam[2] = A[2][2];
-}
-
 __global__ __launch_bounds__(256) void pl_normals_kernel(RfGrid g, const float* __restrict__ pts, int N, int min_nbrs, float vx, float vy, float vz,
                                                          float* __restrict__ normals, int32_t* __restrict__ count, float* __restrict__ curv) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    const float q[3] = {pts[3 * (size_t)i], pts[3 * (size_t)i + 1], pts[3 * (size_t)i + 2]};
+    float q[3];
+    rf_load_row(pts, i, q);
     const double px = (double)q[0], py = (double)q[1], pz = (double)q[2];
-    const int cx = rf_cell(px, g.inv_cell), cy = rf_cell(py, g.inv_cell), cz = rf_cell(pz, g.inv_cell);
-    unsigned slot[27];
-#pragma unroll
-    for (int c = 0; c < 27; ++c) slot[c] = rf_slot(rf_clampi(cx + c % 3 - 1), rf_clampi(cy + (c / 3) % 3 - 1), rf_clampi(cz + c / 9 - 1), g.mask);
-    int n = 0;
-    double s1x = 0.0, s1y = 0.0, s1z = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
-#pragma unroll
-    for (int c = 0; c < 27; ++c) {
-        bool seen = false;
-#pragma unroll
-        for (int k = 0; k < c; ++k) seen = seen || slot[k] == slot[c];
-        if (seen) continue;                                           // a bucket is walked once
-        const int p1 = g.start[slot[c] + 1];
-        for (int p = g.start[slot[c]]; p < p1; ++p) {
-            const float4 v = g.pk[p];
-            const float b[3] = {v.x, v.y, v.z};
-            if (dist2_f32<3>(q, b) < g.gate2) {                       // false for a NaN / inf on either side
-                const double dx = (double)v.x - px, dy = (double)v.y - py, dz = (double)v.z - pz;
-                ++n;
-                s1x += dx; s1y += dy; s1z += dz;
-                sxx += dx * dx; sxy += dx * dy; sxz += dx * dz;
-                syy += dy * dy; syz += dy * dz; szz += dz * dz;
-            }
-        }
-    }
+    int n;
+    double S1[3], S2[6];
+    rf_moments(g, q, n, S1, S2);
     count[i] = n;
     float out[3] = {0.f, 0.f, 0.f}, cv = -1.f;
     if (n >= min_nbrs) {                                              // min_nbrs >= 3 > 0
         const double dn = (double)n;
-        const double C[6] = {sxx - s1x * s1x / dn, sxy - s1x * s1y / dn, sxz - s1x * s1z / dn, syy - s1y * s1y / dn, syz - s1y * s1z / dn, szz - s1z * s1z / dn};
+        const double C[6] = {S2[0] - S1[0] * S1[0] / dn, S2[1] - S1[0] * S1[1] / dn, S2[2] - S1[0] * S1[2] / dn,
+                             S2[3] - S1[1] * S1[1] / dn, S2[4] - S1[1] * S1[2] / dn, S2[5] - S1[2] * S1[2] / dn};      // not divided by n: the vectors are those of C / n
         double lam[3], V[9];
-        pl_eig3(C, lam, V);
+        rf_eig3<true>(C, lam, V);
         int i1 = 0;
         if (lam[1] < lam[i1]) i1 = 1;
         if (lam[2] < lam[i1]) i1 = 2;
@@ -328,8 +267,7 @@ int yoho_estimate_normals(yoho_ctx* c, const float* pts, int N, float radius, in
                           float* curv, void* stream) {
     const char* fn = "yoho_estimate_normals";
     int rc;
-    if ((rc = rf_check_sizes(fn, c, "N", N, 1)) || (rc = rf_check_limit(fn, RF_NAMED(YOHO_REFINE_MAX_POINTS), "N", N)) ||
-        (rc = rf_check_radius(fn, "radius", radius))) return rc;
+    if ((rc = rf_check_cloud(fn, c, N, "radius", radius))) return rc;
     if (min_nbrs < 3) { set_error("yoho_estimate_normals: min_nbrs=%d must be at least 3", min_nbrs); return YOHO_EINVAL; }
     if (!std::isfinite(vx) || !std::isfinite(vy) || !std::isfinite(vz)) {
         set_error("yoho_estimate_normals: viewpoint (%g, %g, %g) must be finite", (double)vx, (double)vy, (double)vz);

@@ -1,5 +1,6 @@
 // THE KABSCH STEP (include/yoho_refine.h) in pieces, shared by refine.hip, plane.hip, verify.hip and consist.hip: the fixed-order f64
-// sums, the rounded transform of a point, centroids, centred products, the 3 x 3 solve, the [R | t] row.  No grid here (rfgrid.h).
+// sums, the rounded transform of a point, centroids, centred products, the 3 x 3 solve, the [R | t] row; and the symmetric 3 x 3
+// eigen-solve of plane.hip's normals and salient.hip's saliency (rf_eig3).  No grid here (rfgrid.h).
 // Include from translation units compiled with -ffp-contract=off only.
 //
 // THE SUMS (the header's "THE SUM").  A pass writes the partial sums of its 256 elements to a slab at its block index (rf_block_sum):
@@ -171,6 +172,51 @@ __device__ inline bool rf_rotation(const double* H, double* R) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) R[i * 3 + j] = v1[i] * u1[j] + v2[i] * u2[j] + v3[i] * u3[j];
     return true;
+}
+
+// ---- the symmetric 3 x 3 eigen-solve -------------------------------------------------------------------------------------------
+// symmetric 3 x 3 (a = {xx, xy, xz, yy, yz, zz}) -> eigenvalues lam[3] (unsorted) and, with VECTORS, eigenvectors as the columns of V
+// (row-major; without, V is not touched and may be null: nine fewer live doubles and a dozen fewer multiplies a rotation): cyclic
+// two-sided Jacobi.  A rotation is skipped once the off-diagonal entry is below 2^-58 of the two diagonal entries it couples: an
+// absolute perturbation that small moves an eigenvalue by no more (Weyl) and turns an eigenvector by 2^-58 / (relative gap), far inside
+// the bounds of tests/test_gpu_plane.py and tests/test_gpu_salient.py.
+template <bool VECTORS>
+__device__ inline void rf_eig3(const double (&a)[6], double (&lam)[3], double* V) {
+    double A[3][3] = {{a[0], a[1], a[2]}, {a[1], a[3], a[4]}, {a[2], a[4], a[5]}};
+    if constexpr (VECTORS) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    }
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int pq = 0; pq < 3; ++pq) {
+            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2, r = 3 - p - q;
+            const double apq = A[p][q];
+            if (fabs(apq) > 0x1p-58 * (fabs(A[p][p]) + fabs(A[q][q]))) {
+                rotated = true;
+                const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
+                const double cs = 1.0 / sqrt(1.0 + t * t), sn = cs * t;
+                A[p][p] -= t * apq;
+                A[q][q] += t * apq;
+                A[p][q] = A[q][p] = 0.0;
+                const double arp = A[r][p], arq = A[r][q];
+                A[r][p] = A[p][r] = cs * arp - sn * arq;
+                A[r][q] = A[q][r] = sn * arp + cs * arq;
+                if constexpr (VECTORS) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const double vp = V[k * 3 + p], vq = V[k * 3 + q];
+                        V[k * 3 + p] = cs * vp - sn * vq;
+                        V[k * 3 + q] = sn * vp + cs * vq;
+                    }
+                }
+            }
+        }
+        if (!rotated) break;
+    }
+    lam[0] = A[0][0]; lam[1] = A[1][1]; lam[2] = A[2][2];
 }
 
 }  // namespace yoho

@@ -1,7 +1,22 @@
-// The cell-sorted grid over a target cloud, as its users see it: the device-side pieces of a query (rf_cell / rf_slot, RfGrid, rf_walk)
-// inline, the workspace and the two host calls that build it (rfgrid.hip, where THE GRID and THE QUERY are described), and the
-// refusals the entries of the family share.  The sums and the Kabsch step are in rffit.h.  Include from translation units compiled
-// with -ffp-contract=off only.
+// The cell-sorted grid over a target cloud, as its users see it: the device-side pieces of a query inline, the workspace and the two
+// host calls that build it (rfgrid.hip, where THE GRID and THE QUERY are described), and the refusals the entries of the family share.
+// The sums, the Kabsch step and the 3 x 3 Jacobi are in rffit.h.  Include from translation units compiled with -ffp-contract=off only.
+//
+//   rf_cell / rf_slot, RfGrid     a coordinate's cell, a cell's bucket, the grid as a kernel argument
+//   rf_load_row, rf_finite3       row i of an (N, 3) f32 cloud; "three coordinates finite" (false for a NaN)
+//   rf_walk                       the nearest candidate inside the gate, ties to the lower row: refine, verify, multiway, fuse, pl_pair_kernel.
+//                                 It may meet a point twice - clamped neighbour cells are the same cell, and two of the 27 can hash to one
+//                                 bucket -, which a minimum does not notice and a count, a list or a sum does
+//   rf_slots27                    THE DISTINCT BUCKETS: the 27 slots around a query in registers, handed one by one to a functor, a slot equal
+//                                 to an earlier one replaced by RF_SEEN.  Every bucket is then walked once, every point of it goes through the exact f32 test, a point
+//                                 lies in one bucket only: a count is exact
+//   rf_walk_each                  f(d2, j) once per candidate (d2 < gate2, j != self): clean.hip's lists, cluster.hip's three passes.  The
+//                                 marked slots are parked in LDS, one column per lane (27 648 bytes a workgroup of 256), and the buckets are
+//                                 walked by a loop that is NOT unrolled: the functor may be a 31-step insertion chain, and 27 copies of it
+//                                 would not fit the instruction cache.  A lane reads its own column only, so no barrier is needed
+//   rf_moments                    the unrolled walk with the slots in registers: n, S1 (3) and S2 (6) of the offsets from the query in
+//                                 f64, the row itself included - plane.hip's normals, salient.hip's saliency.  One lane per point: the ten
+//                                 accumulators need no cross-lane sum, whose order would have to be fixed as well
 #pragma once
 #include "common.h"
 #include "nnmath.h"
@@ -53,6 +68,77 @@ __device__ __forceinline__ void rf_walk(const RfGrid& g, const float (&q)[3], fl
     }
 }
 
+// ---- the distinct buckets (rf_slots27, rf_walk_each, rf_moments) ------------------------------------------------------------------------
+constexpr unsigned RF_SEEN = 0xFFFFFFFFu;      // no slot: a slot is below 2^23
+
+__device__ __forceinline__ void rf_load_row(const float* __restrict__ pts, int i, float (&q)[3]) {
+    q[0] = pts[3 * (size_t)i];
+    q[1] = pts[3 * (size_t)i + 1];
+    q[2] = pts[3 * (size_t)i + 2];
+}
+__device__ __forceinline__ bool rf_finite3(float x, float y, float z) {      // false for a NaN
+    return fabsf(x) < __builtin_inff() && fabsf(y) < __builtin_inff() && fabsf(z) < __builtin_inff();
+}
+
+// f(c, slot) for the 27 cells c around q in order, unrolled; a slot equal to an earlier one comes as RF_SEEN
+template <typename F>
+__device__ __forceinline__ void rf_slots27(const RfGrid& g, const float (&q)[3], F&& f) {
+    const int cx = rf_cell((double)q[0], g.inv_cell), cy = rf_cell((double)q[1], g.inv_cell), cz = rf_cell((double)q[2], g.inv_cell);
+    unsigned slot[27];
+#pragma unroll
+    for (int c = 0; c < 27; ++c) slot[c] = rf_slot(rf_clampi(cx + c % 3 - 1), rf_clampi(cy + (c / 3) % 3 - 1), rf_clampi(cz + c / 9 - 1), g.mask);
+#pragma unroll
+    for (int c = 0; c < 27; ++c) {
+        bool seen = false;
+#pragma unroll
+        for (int k = 0; k < c; ++k) seen = seen || slot[k] == slot[c];
+        f(c, seen ? RF_SEEN : slot[c]);                                   // a bucket is walked once
+    }
+}
+
+// every candidate of q among the grid's points, row `self` left out (-1: none): f(d2, j), each once, in no promised order
+template <typename F>
+__device__ __forceinline__ void rf_walk_each(const RfGrid& g, const float (&q)[3], int self, unsigned (*slots)[256], F&& f) {
+    rf_slots27(g, q, [&](int c, unsigned s) { slots[c][threadIdx.x] = s; });
+#pragma unroll 1
+    for (int c = 0; c < 27; ++c) {
+        const unsigned s = slots[c][threadIdx.x];
+        if (s == RF_SEEN) continue;
+        const int p1 = g.start[s + 1];
+        for (int p = g.start[s]; p < p1; ++p) {
+            const float4 v = g.pk[p];
+            const float b[3] = {v.x, v.y, v.z};
+            const float d2 = dist2_f32<3>(q, b);
+            const int j = __float_as_int(v.w);
+            if (d2 < g.gate2 && j != self) f(d2, j);                      // false for a NaN / inf on either side
+        }
+    }
+}
+
+// the candidates of q, q's own row among them: their number, S1 = SUM d, S2 = SUM d d^T {xx, xy, xz, yy, yz, zz}, d = candidate - q in f64
+__device__ __forceinline__ void rf_moments(const RfGrid& g, const float (&q)[3], int& n, double (&S1)[3], double (&S2)[6]) {
+    const double px = (double)q[0], py = (double)q[1], pz = (double)q[2];
+    n = 0;
+    double s1x = 0.0, s1y = 0.0, s1z = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+    rf_slots27(g, q, [&](int, unsigned s) {
+        if (s == RF_SEEN) return;
+        const int p1 = g.start[s + 1];
+        for (int p = g.start[s]; p < p1; ++p) {
+            const float4 v = g.pk[p];
+            const float b[3] = {v.x, v.y, v.z};
+            if (dist2_f32<3>(q, b) < g.gate2) {                           // false for a NaN / inf on either side
+                const double dx = (double)v.x - px, dy = (double)v.y - py, dz = (double)v.z - pz;
+                ++n;
+                s1x += dx; s1y += dy; s1z += dz;
+                sxx += dx * dx; sxy += dx * dy; sxz += dx * dz;
+                syy += dy * dy; syz += dy * dz; szz += dz * dz;
+            }
+        }
+    });
+    S1[0] = s1x; S1[1] = s1y; S1[2] = s1z;
+    S2[0] = sxx; S2[1] = sxy; S2[2] = sxz; S2[3] = syy; S2[4] = syz; S2[5] = szz;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 struct RfGridWs {
     unsigned nslots; int bits, nblk;
@@ -88,6 +174,12 @@ inline int rf_check_radius(const char* fn, const char* name, float r) {
 }
 inline int rf_check_tol(const char* fn, double tol) { return std::isnan(tol) ? RF_REFUSE("%s: tol is NaN", fn) : 0; }
 inline int rf_check_pointers(const char* fn, bool all_there) { return all_there ? 0 : RF_REFUSE("%s: bad argument (a required pointer is NULL)", fn); }
+// one cloud of at least one point and the radius of its grid: what the entries over a single cloud refuse first, in that order
+inline int rf_check_cloud(const char* fn, const void* c, int N, const char* radius_name, float radius) {
+    int rc;
+    if ((rc = rf_check_sizes(fn, c, "N", N, 1)) || (rc = rf_check_limit(fn, RF_NAMED(YOHO_REFINE_MAX_POINTS), "N", N))) return rc;
+    return rf_check_radius(fn, radius_name, radius);
+}
 // a source and a target cloud of at least one point each
 inline int rf_check_clouds(const char* fn, const void* c, int Ns, int Nt) {
     const int rc = rf_check_sizes(fn, c, "Ns", Ns, 1, "Nt", Nt, 1);
