@@ -52,6 +52,7 @@
  *     csrc/common.h; every value gives valid results):   YOHO_PARTII_TAIL=staged, YOHO_TRANSFER=staged, YOHO_XF_STEAL=0,
  *     YOHO_NN_SPLITS=<n>, YOHO_FCGF=f32 (takes effect at the context's yoho_load_fcgf), YOHO_FCGF_MAPS=full, YOHO_FCGF_NORM=staged, YOHO_FCGF_HEADS=staged, YOHO_PARTII_L1=3 (PartII's first layer on the 256 x 256-tile GEMM kernel),
  *     YOHO_PARTII_CONE=direct (PartII mode 2 keeps the direct 13-element cone kernel instead of the cone GEMM),
+ *     YOHO_FGEMM_TILES=<1..64> (default 16; tiles a workgroup of PartI's two large irrep GEMMs takes before it retires; identical bits for every value),
  *     YOHO_WS_LIMIT_MB=<n> (workspace requests above n MiB fail with YOHO_ENOMEM as on an exhausted device: test hook for the recoveries).
  *     The timing experiments YOHO_PARTI_DEBUG / YOHO_FGEMM_DEBUG exist only in the separate -DYOHO_EXPERIMENTS library, which no
  *     product code loads.

@@ -373,6 +373,7 @@ int yoho_ctx_create(int device, const float* R, const uint8_t* N, const uint8_t*
         if (const char* e = std::getenv("YOHO_WS_LIMIT_MB")) c->env.ws_limit_mb = std::atoll(e);
         if (is("YOHO_PARTII_L1", "3")) c->env.partII_l1_variant = FG_TILE256_W8;
         c->env.partII_cone_direct = is("YOHO_PARTII_CONE", "direct");
+        if (const int n = num("YOHO_FGEMM_TILES")) c->env.fgemm_tiles = n < 1 ? 1 : (n > 64 ? 64 : n);
     }
     if (const char* m = std::getenv("YOHO_FCGF_CELLS")) c->fcgf_cell_sort = std::atoi(m);
     if (const char* m = std::getenv("YOHO_FCGF_SORT")) c->fcgf_parity_sort = std::strcmp(m, "0") == 0 ? 0 : 1;
@@ -420,6 +421,8 @@ int yoho_ctx_create(int device, const float* R, const uint8_t* N, const uint8_t*
     }
     HIPCHK(hipMalloc((void**)&c->d_xfctr, 16 * sizeof(int)));
     HIPCHK(hipMemset(c->d_xfctr, 0, 16 * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&c->d_fgctr, 64 * sizeof(int)));
+    HIPCHK(hipMemset(c->d_fgctr, 0, 64 * sizeof(int)));
     *out = c;
     return 0;
 }
@@ -446,6 +449,7 @@ int yoho_ctx_destroy(yoho_ctx* c) {
     if (c->d_tap_inv) (void)hipFree(c->d_tap_inv);
     if (c->d_rflag) (void)hipFree(c->d_rflag);
     if (c->d_xfctr) (void)hipFree(c->d_xfctr);
+    if (c->d_fgctr) (void)hipFree(c->d_fgctr);
     if (c->d_amax) (void)hipFree(c->d_amax);
     for (int* t : {c->tabs.slabtab, c->tabs.outg, c->tabs.slab4, c->tabs.unitg}) if (t) (void)hipFree(t);
     delete c->fb;
@@ -793,6 +797,8 @@ static int partI_passG_chunk(yoho_ctx* c, char* ws, size_t slice, int evbase, co
     int* xc = c->env.xf_steal ? c->d_xfctr + (size_t)slot * 8 : nullptr;     // ticket counters of this stream slot's three transform launches (a launch leaves them at zero)
     // gconv_mode 7: the two large GEMMs take their correction products on the fp8 pipe and scale their activation operand by the largest
     // magnitude the transform in front of them wrote (am[0]: planes of act(h0) for 256 -> 512, am[1]: planes of act(mid) for 512 -> 256)
+    int* gc = c->env.fgemm_tiles > 1 ? c->d_fgctr + (size_t)slot * 32 : nullptr;   // tile tickets of this stream slot's two large GEMM launches (16 ints each)
+    const int gr = c->env.fgemm_tiles;
     unsigned* am = c->gconv_mode == 7 ? c->d_amax + (size_t)slot * 4 : nullptr;
     if (am) HIPCHK(hipMemsetAsync(am, 0, 4 * sizeof(unsigned), s));
     if ((rc = launch_head16(x, B, nT, bP32, kppad, c->dF16, s, x1, B0, rf))) return rc;
@@ -801,11 +807,11 @@ static int partI_passG_chunk(yoho_ctx* c, char* ws, size_t slice, int evbase, co
     mark(2);
     if ((rc = launch_gft16(bH0, nullptr, bP256, kppad, c->dF16, L[0].bn_s, L[0].bn_t, nT, 32, c->nCU, s, 0, rf, gv, xc, am))) return rc;
     mark(3);
-    if ((rc = launch_fgemm(L[1], bP256, kppad, nT, nullptr, bM, 0, s, rf, gv, am))) return rc;
+    if ((rc = launch_fgemm(L[1], bP256, kppad, nT, nullptr, bM, 0, s, rf, gv, am, gc, gr))) return rc;
     mark(4);
     if ((rc = launch_gft16(bM, nullptr, bP512, kppad, c->dF16, L[1].bn_s, L[1].bn_t, nT, 64, c->nCU, s, 0, rf, gv, xc ? xc + 2 : nullptr, am ? am + 1 : nullptr))) return rc;
     mark(5);
-    if ((rc = launch_fgemm(L[2], bP512, kppad, nT, bH0, bA, EPI_RES, s, rf, gv, am ? am + 1 : nullptr))) return rc;
+    if ((rc = launch_fgemm(L[2], bP512, kppad, nT, bH0, bA, EPI_RES, s, rf, gv, am ? am + 1 : nullptr, gc ? gc + 16 : nullptr, gr))) return rc;
     mark(6);
     if ((rc = launch_gft16(bA, nullptr, bP256, kppad, c->dF16, L[2].bn_s, L[2].bn_t, nT, 32, c->nCU, s, 0, rf, gv, xc ? xc + 4 : nullptr))) return rc;
     mark(7);

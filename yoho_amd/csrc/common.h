@@ -164,7 +164,7 @@ int launch_cgemm(const Layer& L, const char* Bstages, int nslot, const unsigned 
 int launch_gft16_invg(const float* in, float* res0, char* planesG, const int* slot_of, int nslot, const void* Ffrag, const float* bn_s,
                       const float* bn_t, int nTiles, int C8, int nCU, hipStream_t s, int* rflag, unsigned* amax);
 int launch_fgemm(const Layer& L, const char* Bplanes, int kppad, int nT32, const float* res, float* out, int flags, hipStream_t s,
-                 int* rflag = nullptr, FGemmBlocking blocking = FG_TILE128, const unsigned* amax = nullptr);
+                 int* rflag = nullptr, FGemmBlocking blocking = FG_TILE128, const unsigned* amax = nullptr, int* tix = nullptr, int tiles = 1);
 void build_gft16_frags(const FourierBasis& fb, std::vector<unsigned short>& out);
 int gconv_layer(yoho_ctx* c, const float* x, int B, int cin, int cout, const float* W, const float* bias, int transpose, float* y,
                 hipStream_t s);
@@ -301,6 +301,8 @@ struct yoho_env_switches {
     bool fcgf_heads_staged = false;    // YOHO_FCGF_HEADS=staged: the decoder's two 1 x 1 heads as two launches (heads_fused_kernel off); identical bits
     yoho::FGemmBlocking partII_l1_variant = yoho::FG_TILE128;   // YOHO_PARTII_L1=3: PartII's first (Fourier) layer on fgemm3 (FG_TILE256_W8) instead of fgemm2
     bool partII_cone_direct = false;   // YOHO_PARTII_CONE=direct: PartII mode 2 keeps the direct 13-element cone kernel (gconv16_kernel<7,4,2>) instead of the cone GEMM
+    int fgemm_tiles = 16;              // YOHO_FGEMM_TILES=<1..64>: tiles a workgroup of the two large irrep GEMMs (fgemm3k) takes before it retires (1 = one static tile;
+                                       // 16 won the side-by-side benchmark against the parent, profiles/fgemm_multitile.md)
     long long ws_limit_mb = 0;         // YOHO_WS_LIMIT_MB=<n>: a workspace request above n MiB fails as an exhausted device would (0 = no limit):
                                        // lets a test walk the YOHO_ENOMEM recoveries of the backbone (hash-table attempt, table voxelisation)
 };
@@ -343,6 +345,7 @@ struct yoho_ctx {
     int* d_rflag = nullptr;      // fp16 range words (note_range): [0] PartI, [1] PartII; read and cleared by yoho_range_status
     unsigned* d_amax = nullptr;  // gconv_mode 7: largest |plane value| the transforms wrote, per stream slot and layer ([2][4], float bit patterns; zeroed at the head of a pass)
     int* d_xfctr = nullptr;      // chunk tickets of the persistent transform kernel (gft16x work stealing): [stream slot 2][launch 4][2], zero between launches
+    int* d_fgctr = nullptr;      // tile tickets of the two large irrep GEMMs (fgemm3k, gemmf.h FGemmArgs::tix): [stream slot 2][launch 2][16], zero between launches
     int fcgf_cell_sort = 1;      // FCGF backbone: level-0 rows grouped by 8^3-voxel cell inside the pass (gather locality): 0 never, 1 passes of >= 2^18 rows, 2 always
     int fcgf_hash_coords = 0;    // 1: coordinate maps through hash tables even when the clouds fit rank-ordered bitmaps (YOHO_FCGF_COORDS=hash, yoho_set_fcgf_sort cell_sort | 4)
     int fcgf_parity_sort = 1;    // transposed convolutions of the FCGF backbone walk parity-sorted rows (spmaps.hip, spconv.hip); 0: YOHO_FCGF_SORT=0

@@ -38,6 +38,8 @@ struct FGemmArgs {
     float descale;
     int* rflag;           // fp16 range flag: raised when an output coefficient will not fit the consumer's fp16 planes (x HF_ASCALE)
     const unsigned* amax; // gconv_mode 7 (fgemm3c): largest |value| of the B planes as a float bit pattern, left by their producer; null = fgemm3
+    int* tix;             // fgemm3k's tile tickets: [0..7] next slot of XCD x, [8] finished workgroups (all 0 between launches), or null = one static tile per workgroup
+    int tiles;            // with tix: tiles a workgroup takes before it retires (FGEMM_TILES_MAX at most)
 };
 
 template <int I, int N, typename Fn>
@@ -85,6 +87,9 @@ __device__ __forceinline__ bool fg3_map(const FGemmArgs& a, int xcd, int slot, i
     }
     return false;
 }
+
+constexpr int FGEMM_TILES_MAX = 64;   // YOHO_FGEMM_TILES: 1 .. 64 tiles per fgemm3k workgroup
+constexpr int FGEMM_TIX_INTS = 16;    // ints of one launch's ticket counters (FGemmArgs::tix: nine used)
 
 // grid of the work maps: 8 x the longest XCD list, `per_tile` workgroups per 256 x 256 tile
 inline int fgemm_grid(const FGemmArgs& a, int per_tile) {

@@ -366,7 +366,7 @@ int pack_cgemm_weights(const float* W, int cin, int cout, int ntaps, std::vector
 }
 
 void fgemm_fill_args(FGemmArgs& a, const Layer& L, const char* Bplanes, int kppad, int nT32, const float* res, float* out, int* rflag) {
-    a.rflag = rflag; a.amax = nullptr;
+    a.rflag = rflag; a.amax = nullptr; a.tix = nullptr; a.tiles = 1;
     a.A = reinterpret_cast<const char*>(L.wpg); a.B = Bplanes; a.bias = L.bias; a.res = res; a.out = out;
     a.cin = L.cin; a.cout = L.cout; a.kppad = kppad; a.nT32 = nT32; a.descale = L.wpg_descale;
     static const int ROT[NIR_ORD] = {0, 0, 4, 4, 2};
@@ -384,9 +384,10 @@ void fgemm_fill_args(FGemmArgs& a, const Layer& L, const char* Bplanes, int kppa
 // the blockings of the irrep GEMMs: one 256 x 256 tile in four waves (gemmf.hip) | 256 x 128 tiles, two four-wave workgroups per CU
 // (fgemm2: PartII's first layer) | one 256 x 256 tile in eight waves sharing the A stage (fgemm3 / fgemm3s / fgemm3c: PartI's default)
 int launch_fgemm(const Layer& L, const char* Bplanes, int kppad, int nT32, const float* res, float* out, int flags, hipStream_t s, int* rflag,
-                 FGemmBlocking blocking, const unsigned* amax) {
+                 FGemmBlocking blocking, const unsigned* amax, int* tix, int tiles) {
     FGemmArgs a;
     fgemm_fill_args(a, L, Bplanes, kppad, nT32, res, out, rflag);
+    a.tix = tix; a.tiles = tiles;          // fgemm3k alone takes several tiles per workgroup (launch_fgemm3)
     static const int dbg_gemm1 = [] { const char* e = experiment_env("YOHO_PARTI_DEBUG"); return (e && std::strstr(e, "gemm1")) ? 1 : 0; }();
     if (dbg_gemm1) blocking = FG_TILE256_W4;
     // fgemm3c and its fp8 weight pack - chosen AFTER every override of the blocking: the other kernels read A as fp16 planes

@@ -340,11 +340,8 @@ __device__ __forceinline__ void read_open32(const char* pa, const char* pb, Frag
     else b.bl[R - 6] = *reinterpret_cast<const uintx4*>(pb + 16384 + (R - 6) * 256);
 }
 
-// One K32 stage on B fragments `b` and A fragments read from pa (block row 0 already in fa[0]); npa / npb: the next stage in LDS, whose
-// opening fragments go to fa[0] / nb; DMA: the wave's pieces of the stage two ahead go to dmabuf (this stage's buffer)
-template <bool DMA>
-__device__ __forceinline__ void step32(const Dma3k& dm, floatx4 (&acc)[8][4], FragsA32 (&fa)[2], const FragsB32& b, FragsB32& nb, const char* pa,
-                                       const char* npa, const char* npb, const char* srcA, const char* srcB, char* dmabuf) {
+// block rows 0..6 of a K32 stage on B fragments `b` and A fragments read from pa (block row 0 already in fa[0])
+__device__ __forceinline__ void rows32(floatx4 (&acc)[8][4], FragsA32 (&fa)[2], const FragsB32& b, const char* pa) {
     sfor<0, 7>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         row_products32(acc[i], fa[i & 1].al, fa[i & 1].ah, b.bh, b.bl, [&](auto mc) {
@@ -354,9 +351,22 @@ __device__ __forceinline__ void step32(const Dma3k& dm, floatx4 (&acc)[8][4], Fr
             if constexpr (m == 2) fa[(i + 1) & 1].ah = *reinterpret_cast<const uintx4*>(pa + (i + 1) * 256);
         });
     });
+}
+// the stage's one wait and barrier: every wave has all of the stage in registers, the next stage has landed
+__device__ __forceinline__ void stage_barrier32() {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
+}
+
+// One K32 stage; npa / npb: the next stage in LDS, whose opening fragments go to fa[0] / nb; DMA: the wave's pieces of the stage two
+// ahead go to dmabuf (this stage's buffer); pre() runs in front of the stage's wait (the ticket of the next tile is published there)
+template <bool DMA, typename Pre>
+__device__ __forceinline__ void step32(const Dma3k& dm, floatx4 (&acc)[8][4], FragsA32 (&fa)[2], const FragsB32& b, FragsB32& nb, const char* pa,
+                                       const char* npa, const char* npb, const char* srcA, const char* srcB, char* dmabuf, Pre&& pre) {
+    rows32(acc, fa, b, pa);
+    pre();
+    stage_barrier32();
     row_products32(acc[7], fa[1].al, fa[1].ah, b.bh, b.bl, [&](auto mc) {
         constexpr int m = decltype(mc)::value;
         if constexpr (m < 5) {                  // two per MFMA: the next stage's first MFMA waits for all ten
@@ -367,71 +377,161 @@ __device__ __forceinline__ void step32(const Dma3k& dm, floatx4 (&acc)[8][4], Fr
     });
 }
 
+template <bool DMA>
+__device__ __forceinline__ void step32(const Dma3k& dm, floatx4 (&acc)[8][4], FragsA32 (&fa)[2], const FragsB32& b, FragsB32& nb, const char* pa,
+                                       const char* npa, const char* npb, const char* srcA, const char* srcB, char* dmabuf) {
+    step32<DMA>(dm, acc, fa, b, nb, pa, npa, npb, srcA, srcB, dmabuf, [] {});
+}
+
+// The last stage of a tile.  Behind its barrier every wave holds the stage in registers and BOTH buffers are dead: nothing is read from
+// them any more (there is no next stage to open), and when the workgroup has a next tile (`next`, wave uniform) that tile's stages 0 and 1
+// go out here, behind block row 7's MFMAs - their latency then runs under this tile's epilogue instead of in front of the next K loop.
+__device__ __forceinline__ void step32_last(const Dma3k& dm, floatx4 (&acc)[8][4], FragsA32 (&fa)[2], const FragsB32& b, const char* pa, bool next,
+                                            const char* nsrcA, const char* nsrcB, char* smem) {
+    rows32(acc, fa, b, pa);
+    stage_barrier32();
+    if (next) {
+        row_products32(acc[7], fa[1].al, fa[1].ah, b.bh, b.bl, [&](auto mc) {
+            constexpr int m = decltype(mc)::value;
+            if constexpr (m < Dma3k::NP) {
+                dm.template piece<m>(nsrcA, nsrcB, smem);
+                dm.template piece<m>(nsrcA + FG_STAGE, nsrcB + FG_STAGE, smem + F3K_BUF);
+            }
+        });
+    } else {
+        row_products32(acc[7], fa[1].al, fa[1].ah, b.bh, b.bl, [](auto) {});
+    }
+}
+
+// A tile of the work map as its workgroup's waves see it (all wave uniform: SGPRs)
+struct Tile3k {
+    const char *Ag, *Bg;
+    int d, KS, row0, kp0, jidx, qbase;
+};
+__device__ __forceinline__ bool tile3k(const FGemmArgs& a, int xcd, int slot, int w8, Tile3k& T) {
+    int t = 0, local = 0, r = 0;
+    if (!fg3_map(a, xcd, slot, t, local, r)) return false;
+    T.d = a.dim[t];
+    const int MT = a.MT[t];
+    T.KS = T.d * a.cin / 32;
+    const int cg = local / MT, mtile = local - cg * MT;
+    const int ntile = r + 8 * cg;
+    T.Ag = a.A + a.a_off[t] + (size_t)mtile * T.KS * FG_STAGE;
+    T.Bg = a.B + a.b_off[t] + (size_t)ntile * T.KS * FG_STAGE;
+    const int wm = (w8 & 3) >> 1, wn = w8 & 1, nh = w8 >> 2;            // Wave3's arrangement
+    T.row0 = mtile * 256 + wm * 128;
+    const int colbase = ntile * 256 + nh * 128 + wn * 64;
+    T.jidx = colbase / a.kppad; T.kp0 = colbase - T.jidx * a.kppad; T.qbase = a.qbase[t];
+    return true;
+}
+
+// Threads 0..7 issue the draw, thread x on XCD x's counter; only the workgroup's own XCD adds 1, the others add 0.  With ONE thread on an
+// address the compiler knows to be wave uniform it funnels the add through a lane of its own choice and broadcasts the answer with a
+// readfirstlane behind vmcnt(0): a wait for the whole round trip at the head of the K loop.  Per-lane addresses keep the answer in the
+// thread's register until it is used.
+__device__ __forceinline__ int draw_ticket(int* tix, int tid, int xcd) {
+    return tid < 8 ? __hip_atomic_fetch_add(tix + tid, tid == xcd ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+}
+
+constexpr int F3K_TICKET = F3K_LDS;            // LDS byte offset of the ticket word
+constexpr int F3K_LDS_ALL = F3K_LDS + 16;
+
+// Tiles per workgroup.  With FGemmArgs::tix set a workgroup runs up to FGemmArgs::tiles tiles and then retires (a workgroup that stayed
+// for the whole launch would leave the other stream's kernels nothing but launch boundaries to get a CU at).  The tiles are TAKEN, one
+// by one and in the work map's order: tix[x] is XCD x's next slot, drawn with a relaxed fetch-add (draw_ticket) and passed to the other
+// waves through the word behind the stage buffers.  The draw for the next tile goes out at the head of this tile's K loop and is
+// published in front of the second-last stage's barrier (any wait the compiler puts in front of that LDS write is the stage's own
+// vmcnt(0)), so at the last stage's barrier the next tile is known and its DMA starts there (step32_last): dispatch, DMA latency,
+// residual loads and the drain of this tile's stores overlap instead of adding up.  The last workgroup out (tix[8] counts them) leaves
+// the counters at zero for the next launch, as gft16x does.  tix == null: one tile, static slot blockIdx.x >> 3.
 __global__ __launch_bounds__(512, 2) void fgemm3k_kernel(FGemmArgs a, int flags) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int t = 0, local = 0, r = 0;
-    if (!fg3_map(a, blockIdx.x & 7, blockIdx.x >> 3, t, local, r)) return;
-    const int d = a.dim[t];
-    const int MT = a.MT[t], KS = d * a.cin / 32;
-    const int cg = local / MT, mtile = local - cg * MT;
-    const int ntile = r + 8 * cg;
-    const char* Ag = a.A + a.a_off[t] + (size_t)mtile * KS * FG_STAGE;
-    const char* Bg = a.B + a.b_off[t] + (size_t)ntile * KS * FG_STAGE;
-    const int wm = (w8 & 3) >> 1, wn = w8 & 1, nh = w8 >> 2;            // Wave3's arrangement
+    const int xcd = blockIdx.x & 7;
+    int* tw = reinterpret_cast<int*>(smem + F3K_TICKET);
+    int slot = blockIdx.x >> 3;
+    if (a.tix) {
+        const int tk = draw_ticket(a.tix, tid, xcd);
+        if (tid == xcd) *tw = tk;
+        __syncthreads();
+        slot = __builtin_amdgcn_readfirstlane(*tw);
+    }
     const Dma3k dm(w8, lane);
-    const int lane_a = (lane >> 4) * 4096 + (wm * 128 + (lane & 15)) * 16;
-    const int lane_b = FG_STAGE + (lane >> 4) * 4096 + (nh * 128 + wn * 64 + (lane & 15)) * 16;
-
-    floatx4 acc[8][4];
-    zero_acc(acc);
-    auto dma = [&](int st, int buf) {
-        const char* sa = uniform_ptr(Ag + (size_t)st * FG_STAGE);
-        const char* sb = uniform_ptr(Bg + (size_t)st * FG_STAGE);
+    const int lane_a = (lane >> 4) * 4096 + (((w8 & 3) >> 1) * 128 + (lane & 15)) * 16;
+    const int lane_b = FG_STAGE + (lane >> 4) * 4096 + ((w8 >> 2) * 128 + (w8 & 1) * 64 + (lane & 15)) * 16;
+    auto dma = [&](const Tile3k& U, int st, int buf) {
+        const char* sa = uniform_ptr(U.Ag + (size_t)st * FG_STAGE);
+        const char* sb = uniform_ptr(U.Bg + (size_t)st * FG_STAGE);
         sfor<0, Dma3k::NP>([&](auto uc) { dm.template piece<decltype(uc)::value>(sa, sb, smem + buf); });
     };
-    dma(0, 0);
-    if (KS > 1) dma(1, F3K_BUF);
-    const int row0 = mtile * 256 + wm * 128, colbase = ntile * 256 + nh * 128 + wn * 64;
-    const bool rows_live = row0 < d * a.cout;       // else: all 128 rows of this wave are padding
-    const int jidx = colbase / a.kppad, kp0 = colbase - jidx * a.kppad, qbase = a.qbase[t];
-    if ((flags & EPI_RES) && rows_live) residual_start(acc, row0, kp0, jidx, d, qbase, a.res, a.descale, a.cout, a.nT32, lane);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (!rows_live) {
-        // keep the wave's share of the DMA and the barriers going: one barrier per stage, as the live waves
-        for (int s = 0; s < KS; ++s) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            if (s + 2 < KS) dma(s + 2, (s & 1) * F3K_BUF);
-        }
+    Tile3k T;
+    bool have = tile3k(a, xcd, slot, w8, T);
+    if (have) {                                    // KS >= 8 and even (cin >= 256, cin % 64 == 0: fgemm_layer_k32)
+        dma(T, 0, 0);
+        dma(T, 1, F3K_BUF);
+    }
+    floatx4 acc[8][4];
+    for (int left = a.tix ? a.tiles : 1; have;) {
+        const bool draw = --left > 0;              // this workgroup may take another tile
+        zero_acc(acc);
+        const bool rows_live = T.row0 < T.d * a.cout;       // else: all 128 rows of this wave are padding (launch_fgemm3: only without tickets)
+        if ((flags & EPI_RES) && rows_live) residual_start(acc, T.row0, T.kp0, T.jidx, T.d, T.qbase, a.res, a.descale, a.cout, a.nT32, lane);
+        // a tile behind the first: this wait also drains the previous tile's stores, which were issued behind this tile's DMA (a counted
+        // wait that leaves them to the first stage's vmcnt(0) was measured and gains nothing: profiles/fgemm_multitile.md)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        return;
-    }
+        __builtin_amdgcn_s_barrier();
+        if (!rows_live) {
+            // keep the wave's share of the DMA and the barriers going: one barrier per stage, as the live waves
+            for (int s = 0; s < T.KS; ++s) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                if (s + 2 < T.KS) dma(T, s + 2, (s & 1) * F3K_BUF);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            return;
+        }
 
-    FragsA32 fa[2];
-    FragsB32 P, Q;
-    sfor<0, 10>([&](auto rc) { read_open32<decltype(rc)::value>(smem + lane_a, smem + lane_b, fa[0], P); });
-    int s = 0, cur = 0;
-    auto run = [&](auto dmac, const FragsB32& b, FragsB32& nb) {
-        const int nxt = cur ^ F3K_BUF;
-        if constexpr (decltype(dmac)::value)
-            step32<true>(dm, acc, fa, b, nb, smem + cur + lane_a, smem + nxt + lane_a, smem + nxt + lane_b, uniform_ptr(Ag + (size_t)(s + 2) * FG_STAGE),
-                         uniform_ptr(Bg + (size_t)(s + 2) * FG_STAGE), smem + cur);
-        else    // the last two stages stage nothing; behind the last one the "next" fragments are read from the other buffer and never used
-            step32<false>(dm, acc, fa, b, nb, smem + cur + lane_a, smem + nxt + lane_a, smem + nxt + lane_b, nullptr, nullptr, nullptr);
-        cur = nxt; ++s;
-    };
-    constexpr std::true_type dmay;
-    constexpr std::false_type dman;
-    while (s + 2 < KS) {                       // KS is even (cin % 64 == 0, launch_fgemm3)
-        run(dmay, P, Q);
-        run(dmay, Q, P);
+        FragsA32 fa[2];
+        FragsB32 P, Q;
+        sfor<0, 10>([&](auto rc) { read_open32<decltype(rc)::value>(smem + lane_a, smem + lane_b, fa[0], P); });
+        const int tk = draw ? draw_ticket(a.tix, tid, xcd) : 0;
+        int s = 0, cur = 0;
+        auto run = [&](auto dmac, const FragsB32& b, FragsB32& nb, auto&& pre) {
+            const int nxt = cur ^ F3K_BUF;
+            if constexpr (decltype(dmac)::value)
+                step32<true>(dm, acc, fa, b, nb, smem + cur + lane_a, smem + nxt + lane_a, smem + nxt + lane_b, uniform_ptr(T.Ag + (size_t)(s + 2) * FG_STAGE),
+                             uniform_ptr(T.Bg + (size_t)(s + 2) * FG_STAGE), smem + cur, pre);
+            else    // the last two stages stage nothing of this tile
+                step32<false>(dm, acc, fa, b, nb, smem + cur + lane_a, smem + nxt + lane_a, smem + nxt + lane_b, nullptr, nullptr, nullptr, pre);
+            cur = nxt; ++s;
+        };
+        constexpr std::true_type dmay;
+        constexpr std::false_type dman;
+        auto nothing = [] {};
+        while (s + 2 < T.KS) {
+            run(dmay, P, Q, nothing);
+            run(dmay, Q, P, nothing);
+        }
+        run(dman, P, Q, [&] { if (draw && tid == xcd) *tw = tk; });
+        Tile3k N = T;
+        const bool next = draw && tile3k(a, xcd, __builtin_amdgcn_readfirstlane(*tw), w8, N);
+        step32_last(dm, acc, fa, Q, smem + cur + lane_a, next, uniform_ptr(N.Ag), uniform_ptr(N.Bg), smem);
+        coef_epilogue(acc, T.row0, T.kp0, T.jidx, T.d, T.qbase, a.out, a.bias, a.descale, a.cout, a.nT32, a.rflag, lane, flags);
+        T = N; have = next;
     }
-    run(dman, P, Q);
-    run(dman, Q, P);
-    coef_epilogue(acc, row0, kp0, jidx, d, qbase, a.out, a.bias, a.descale, a.cout, a.nT32, a.rflag, lane, flags);
+    if (a.tix && tid == 0) {
+        // Every ticket this workgroup drew has been answered (its value was used) before it reports; the last workgroup to report leaves the
+        // counters at zero.  All of it relaxed: the counters are touched by nothing but agent-scope atomics, which are carried out at the
+        // memory side in the order their answers imply, and they order no other data (the next launch starts behind this kernel's end).
+        // An acquire / release report costs an L2 write-back and invalidate per retiring workgroup - measured: 0.05 - 0.2 ms per launch,
+        // more than the loop saves (profiles/fgemm_multitile.md).
+        const int done = __hip_atomic_fetch_add(a.tix + 8, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (done == (int)gridDim.x - 1) {
+#pragma unroll
+            for (int x = 0; x < 9; ++x) __hip_atomic_store(a.tix + x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1021,7 +1121,7 @@ int fgemm3_init() {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm3s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm3c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F3_LDS));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm3k_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F3K_LDS));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fgemm3k_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F3K_LDS_ALL));
     return 0;
 }
 
@@ -1036,7 +1136,28 @@ int launch_fgemm3(const FGemmArgs& a, int flags, hipStream_t s) {
     static const bool small_ok = [] { const char* e = experiment_env("YOHO_FGEMM_DEBUG"); return !(e && std::strstr(e, "nosmall")); }();
     if (small_ok && a.cout == 32 && !(flags & EPI_RES)) hipLaunchKernelGGL(fgemm3s_kernel, dim3(tot), dim3(512), F3_LDS, s, a, flags);
     else if (a.amax) hipLaunchKernelGGL(fgemm3c_kernel, dim3(tot), dim3(512), F3_LDS, s, a, flags);      // gconv_mode 7: corrections on the fp8 pipe
-    else if (flags & F2_K32) hipLaunchKernelGGL(fgemm3k_kernel, dim3(tot), dim3(512), F3K_LDS, s, a, flags);
+    else if (flags & F2_K32) {
+        // several tiles per workgroup (fgemm3k_kernel): 8 x ceil(longest XCD list / R) workgroups draw their slots from a.tix.  Every wave of
+        // such a workgroup must have live rows (cout % 256 == 0: the kernel's idle waves leave at their tile's end); R = 1 is the static map
+        FGemmArgs k = a;
+        if (const char* dbg = experiment_env("YOHO_FGEMM_DEBUG"))
+            if (const char* e = std::strstr(dbg, "tiles=")) k.tiles = std::atoi(e + 6);
+        k.tiles = k.tiles < 1 ? 1 : (k.tiles > FGEMM_TILES_MAX ? FGEMM_TILES_MAX : k.tiles);
+        if (k.tiles == 1 || k.cout % 256) { k.tix = nullptr; k.tiles = 1; }
+        // Workgroups per XCD: ceil(longest list / R) have room for every tile, but a workgroup takes its R tiles one after the other, so
+        // with exactly that many the last ones dispatched walk the end of the list alone while the CUs around them have nothing left to
+        // start (measured: + 8 % on 512 -> 256 at R = 4).  One spare workgroup per other CU of the XCD keeps every CU supplied as long as
+        // tickets remain; a spare that finds none retires at once.
+        // A list no longer than the XCD's CUs keeps the static map: every tile has a CU to itself, a second tile in a workgroup only waits.
+        static const int cu_xcd = [] {
+            int dev = 0, n = 0;
+            return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8 ? n / 8 : 32;
+        }();
+        if (tot / 8 <= cu_xcd) { k.tix = nullptr; k.tiles = 1; }
+        const int need = (tot / 8 + k.tiles - 1) / k.tiles + cu_xcd - 1;
+        const int grid = k.tix ? 8 * (need < tot / 8 ? need : tot / 8) : tot;
+        hipLaunchKernelGGL(fgemm3k_kernel, dim3(grid), dim3(512), F3K_LDS_ALL, s, k, flags);
+    }
     else hipLaunchKernelGGL(fgemm3_kernel, dim3(tot), dim3(512), F3_LDS, s, a, flags);
     HIPCHK(hipGetLastError());
     return 0;
